@@ -14,6 +14,11 @@ the ranks (strong scaling: same 1M problem), each rank selects its local top-2m 
 and merged with the (criterion asc, id desc) rule.
 
 Smaller problems for quick checks: --n-seqs / --n-pos.
+
+A plain run sets up, warms up, times --steps steps and prints the result line (metric, value, ms_per_step, the hit checksum).
+--dump-outputs DIR writes the hit lists of the last timed step as DIR/hits_<field>.npy.  Everything else the benchmark
+measures - the roofline passes of the sweep kernels, the CPU baseline, the dense-profile roofline and the end-to-end trees and
+complete pipelines - runs with --full only (the --no-* options below then leave parts of it out).
 """
 import argparse
 import json
@@ -42,6 +47,10 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--n-seqs", type=int, default=1000000)
     ap.add_argument("--n-pos", type=int, default=200)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the hit lists of the last timed step (every seed's top-k records) to DIR/hits_<field>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline passes, the CPU baseline, the dense-profile roofline and the end-to-end legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end trees (wall-clock half of the metric)")
     ap.add_argument("--no-e2e-c4", action="store_true", help="skip the 1M x 200 end-to-end tree (minutes), keep C3's")
@@ -49,7 +58,9 @@ def parse():
     ap.add_argument("--no-e2e-full", action="store_true", help="skip the complete pipelines of configs C2, C5 and C4 (~17 minutes)")
     ap.add_argument("--no-e2e-c4-full", action="store_true", help="skip the complete -nt pipeline of config C4 (1M x 200; ~9 minutes on one GPU)")
     ap.add_argument("--no-e2e-c5-one-thread", action="store_true", help="skip config C5's complete pipeline in the reference's one-thread order (~6 minutes)")
-    ap.add_argument("--time-budget", type=float, default=1500.0, help="seconds after which the remaining complete pipelines are skipped (and reported as skipped)")
+    ap.add_argument("--time-budget", type=float, default=540.0,
+                    help="--full: seconds after which the remaining end-to-end legs are skipped (and reported as skipped); a leg still "
+                         "running 30 s past it is stopped and reported as such")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)   # (internal: "main" = the step measurement alone, or the key of one end-to-end leg)
     ap.add_argument("--in-process", action="store_true", help="run the end-to-end legs inside this process instead of one child process each")
     return ap.parse_args()
@@ -390,6 +401,112 @@ def end_to_end_full(which, device, one_thread, comm=None):
     return out
 
 
+def dump_outputs(out_dir, last):
+    """--dump-outputs: what the timed path returned in its last step - every seed's top-k hit records - as DIR/hits_<field>.npy,
+    one [seeds, k] array per field: ids as float64 (exact; -1 marks an empty slot), distance, weight and criterion in the
+    precision the kernels computed them in.  8 x 2 000 records at the headline size, well under a megabyte."""
+    os.makedirs(out_dir, exist_ok=True)
+    hits = np.stack(last)
+    for f in hits.dtype.names:
+        a = hits[f]
+        a = a.astype(np.float64 if a.dtype.kind in "iu" or a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(out_dir, "hits_%s.npy" % f), np.ascontiguousarray(a))
+
+
+def step_roofline(args, ops, state, seeds, k, lo, hi, world, elapsed, use_dist, one_step):
+    """--full: the roofline of the sweep kernels on the headline workload, from passes of their own after the timed steps"""
+    n, L = args.n_seqs, args.n_pos
+    # A sweep is ONE launch over all targets (vft_kernels_nj.h): k_sweep_nt<MODE_CRIT_LEAFQ> for a leaf seed, k_sweep_nt_both for a
+    # profile seed - the profile x profile ProfileDist over the internal targets with the table walk over the leaf targets riding on
+    # the same CUs.  Timed with HIP events on the kernels' own stream over one more pass per kind of seed (events between the
+    # launches would open gaps in main's timed region); the roofline prices the average launch against its algorithmic bytes.
+    seeds_leaf = np.asarray([q for q in seeds if q < n], np.int64)
+    seeds_prof = np.asarray([q for q in seeds if q >= n], np.int64)
+
+    def timed_pass(which):
+        ops.timer_start()
+        ops.setBestHitBatch(which, state.n_active, state.n_diff_allow, state.totdiam, k)
+        ops.timer_stop_ms()
+        return ops.sweep_kernel_ms() + (ops.sweep_kernel_sweeps(),)
+
+    # (a launch can stand for several sweeps: runs of leaf seeds share a pass over the targets, k_sweep_nt_leafq_multi)
+    leaf_ms, n_leaf_launches, n_leaf_sweeps = timed_pass(seeds_leaf) if len(seeds_leaf) and not use_dist else (0.0, 0, 0)
+    prof_ms, n_prof_launches, n_prof_sweeps = timed_pass(seeds_prof) if len(seeds_prof) and not use_dist else (0.0, 0, 0)
+    if use_dist:   # (sharded: one instrumented step as it is)
+        ops.timer_start()
+        one_step()
+        ops.timer_stop_ms()
+        kern_ms, launches = ops.sweep_kernel_ms()
+        sweeps = ops.sweep_kernel_sweeps()
+    else:
+        launches = n_leaf_launches + n_prof_launches
+        sweeps = n_leaf_sweeps + n_prof_sweeps
+        kern_ms = (leaf_ms * n_leaf_launches + prof_ms * n_prof_launches) / max(launches, 1)
+    ab = state.algorithmic_bytes_per_sweep(lo, hi)
+    sweeps_per_launch = sweeps / max(launches, 1)
+    alg_sweep = float(ab["leaf"] + ab["internal"])            # the algorithm's bytes of ONE seed's sweep (SURVEY 8d)
+    alg_main = alg_sweep * sweeps_per_launch                  # ... times the sweeps an average launch processes
+    moved_main = float(ab["moved_leaf"] + ab["moved_internal"])   # what one pass over the targets moves, however many seeds ride on it
+    # Counters of the same kernels from the rocprofv3 PMC passes kept under profiles/ (rocprofv3 cannot run inside this process;
+    # tools/profile_round.sh + tools/profile_collect.py -> profiles/traffic.json, used only while the hash of the sweep kernels'
+    # sources recorded there still matches - counters read from other kernel sources say nothing: null):
+    #   HBM bytes per launch = FETCH_SIZE x 2 (the counter's gfx950 correction) + WRITE_SIZE
+    #   VALU instructions per launch = SQ_INSTS_VALU (wavefront instructions; x 64 lanes)
+    traffic = None
+    pmc = {}
+    tpath = os.path.join(ROOT, "profiles", "traffic.json")
+    if os.path.exists(tpath) and (n, L, world) == (1000000, 200, 1):
+        t = json.load(open(tpath))
+        if t.get("kernel_sources_sha256") == sweep_kernel_hash():
+            pmc = t.get("sweep_launch_average", {})
+            traffic = pmc.get("bytes_per_launch")
+    # peak VALU issue: 256 CUs x 4 SIMDs x 16 lanes per cycle x 2.4 GHz (MI355X) = 3.93e13 lane-instructions/s
+    VALU_PEAK = 256 * 64 * 2.4e9
+
+    def per_kind(ms, nl, ns, key):
+        spl = ns / max(nl, 1)
+        rec = pmc.get(key, {})
+        out = dict(avg_launch_ms=ms, sweeps_per_launch=spl,
+                   algorithmic_equiv_gbs=alg_sweep * spl / (ms * 1e-3) / 1e9 if ms > 0 else 0.0,
+                   moved_model_gbs=moved_main / (ms * 1e-3) / 1e9 if ms > 0 else 0.0)
+        if rec.get("bytes_per_launch") and ms > 0:
+            out["hbm_bytes_per_launch_pmc"] = int(rec["bytes_per_launch"])
+            out["hbm_frac_physical"] = rec["bytes_per_launch"] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS
+        if rec.get("valu_wave_insts_per_launch") and ms > 0:
+            out["valu_lane_insts_per_launch"] = int(rec["valu_wave_insts_per_launch"] * 64)
+            out["valu_frac"] = rec["valu_wave_insts_per_launch"] * 64 / (ms * 1e-3) / VALU_PEAK
+            if rec.get("valu_busy_frac_pmc") is not None:
+                out["valu_busy_frac_pmc"] = rec["valu_busy_frac_pmc"]
+        return out
+
+    # `achieved` / `frac` price what the memory system SEES: the bytes one launch moves (the PMC figure while it belongs to these
+    # kernel sources, else the layout model of workload.py) / the launch's duration - never above the peak.  With S seeds sharing a
+    # pass (vft_sweep_batch) the algorithm's own byte count, SURVEY 8(d)'s per-sweep figure x the sweeps a launch carries, is an
+    # EQUIVALENT rate only (`algorithmic_equiv_gbs`: what a seed-by-seed stream would have to sustain) and is not divided by the peak.
+    phys = float(traffic) if traffic else moved_main
+    achieved = phys / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+    valu = None
+    if pmc.get("valu_wave_insts_per_launch") and kern_ms > 0:
+        li = pmc["valu_wave_insts_per_launch"] * 64.0
+        valu = dict(lane_insts_per_launch=int(li), achieved_lane_insts_per_s=li / (kern_ms * 1e-3), peak_lane_insts_per_s=VALU_PEAK,
+                    frac=li / (kern_ms * 1e-3) / VALU_PEAK, source="profiles/traffic.json (rocprofv3 --pmc SQ_INSTS_VALU)")
+    roofline = dict(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
+                    traffic=traffic, bytes_source="pmc" if traffic else "layout_model",
+                    limited_by="valu (instruction issue: S seeds share one pass over the targets, the stream is read once per S sweeps)",
+                    valu=valu,
+                    kernel="k_sweep_nt_profq_multi<float,4> (four profile seeds per launch) / k_sweep_nt_leafq_multi<float,4> (four leaf seeds per launch)",
+                    launches=int(launches), sweeps=int(sweeps), sweeps_per_launch=sweeps_per_launch, avg_launch_ms=kern_ms,
+                    algorithmic_bytes_per_sweep=int(alg_sweep), algorithmic_bytes_per_launch=int(alg_main),
+                    algorithmic_equiv_gbs=alg_main / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0,
+                    moved_bytes_per_launch_model=int(moved_main),
+                    phi=ab["phi"],
+                    profile_seed_launch=per_kind(prof_ms, n_prof_launches, n_prof_sweeps, "profile_seed_instance") if not use_dist else None,
+                    leaf_seed_launch=per_kind(leaf_ms, n_leaf_launches, n_leaf_sweeps, "leaf_seed_instance") if not use_dist else None,
+                    step=dict(algorithmic_bytes=int(alg_sweep * len(seeds)), algorithmic_equiv_gbs=alg_sweep * len(seeds) / (elapsed / args.steps) / 1e9))
+    assert roofline["frac"] <= 1.0, "a physical fraction above the peak: the byte count is wrong"
+    return roofline
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` without a launcher around it: start the N ranks as CHILD processes (torch.distributed.run,
     one per GPU, rendezvous on 127.0.0.1) before anything in this process touches the GPU, relay what they print and exit
@@ -460,7 +577,12 @@ def launch_legs(args):
             print(json.dumps(line), flush=True)
             continue
         print("bench.py: %.0f s - %s" % (used, key), file=sys.stderr, flush=True)
-        r = subprocess.run([sys.executable, me, "--child", key], stdout=subprocess.PIPE)
+        try:   # (a leg that runs far past its estimate must not take the whole run past the budget)
+            r = subprocess.run([sys.executable, me, "--child", key], stdout=subprocess.PIPE, timeout=max(1.0, args.time_budget + 30.0 - used))
+        except subprocess.TimeoutExpired:
+            line[key] = {"workload": which, "error": "stopped at %.0f s, 30 s past the time budget of %.0f s" % (time.perf_counter() - T_START, args.time_budget)}
+            print(json.dumps(line), flush=True)
+            continue
         recs = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
         if r.returncode == 0 and recs:
             line[key] = json.loads(recs[-1])
@@ -500,6 +622,8 @@ def main():
         return
     if args.child and args.child != "main":
         return run_leg(args.child)
+    if not args.full:   # a plain run: the step measurement alone, in this process
+        args.no_cpu_baseline = args.no_dense = args.no_e2e = True
     # (the end-to-end legs belong to the headline workload: a reduced --n-seqs / --n-pos run is the step measurement alone, in this process)
     if single and args.child is None and not args.in_process and not args.no_e2e and (args.n_seqs, args.n_pos) == (1000000, 200) and wanted_legs(args):
         return launch_legs(args)
@@ -596,95 +720,8 @@ def main():
 
     ops_per_step = len(seeds) * state.n_active
     value = ops_per_step * args.steps / elapsed
-
-    # A sweep is ONE launch over all targets (vft_kernels_nj.h): k_sweep_nt<MODE_CRIT_LEAFQ> for a leaf seed, k_sweep_nt_both for a
-    # profile seed - the profile x profile ProfileDist over the internal targets with the table walk over the leaf targets riding on
-    # the same CUs.  Timed with HIP events on the kernels' own stream over one more pass per kind of seed (events between the
-    # launches would open gaps in the timed region above); the roofline prices the average launch against its algorithmic bytes.
-    seeds_leaf = np.asarray([q for q in seeds if q < n], np.int64)
-    seeds_prof = np.asarray([q for q in seeds if q >= n], np.int64)
-
-    def timed_pass(which):
-        ops.timer_start()
-        ops.setBestHitBatch(which, state.n_active, state.n_diff_allow, state.totdiam, k)
-        ops.timer_stop_ms()
-        return ops.sweep_kernel_ms() + (ops.sweep_kernel_sweeps(),)
-
-    # (a launch can stand for several sweeps: runs of leaf seeds share a pass over the targets, k_sweep_nt_leafq_multi)
-    leaf_ms, n_leaf_launches, n_leaf_sweeps = timed_pass(seeds_leaf) if len(seeds_leaf) and not use_dist else (0.0, 0, 0)
-    prof_ms, n_prof_launches, n_prof_sweeps = timed_pass(seeds_prof) if len(seeds_prof) and not use_dist else (0.0, 0, 0)
-    if use_dist:   # (sharded: one instrumented step as it is)
-        ops.timer_start()
-        one_step()
-        ops.timer_stop_ms()
-        kern_ms, launches = ops.sweep_kernel_ms()
-        sweeps = ops.sweep_kernel_sweeps()
-    else:
-        launches = n_leaf_launches + n_prof_launches
-        sweeps = n_leaf_sweeps + n_prof_sweeps
-        kern_ms = (leaf_ms * n_leaf_launches + prof_ms * n_prof_launches) / max(launches, 1)
-    ab = state.algorithmic_bytes_per_sweep(lo, hi)
-    sweeps_per_launch = sweeps / max(launches, 1)
-    alg_sweep = float(ab["leaf"] + ab["internal"])            # the algorithm's bytes of ONE seed's sweep
-    alg_main = alg_sweep * sweeps_per_launch                  # ... times the sweeps an average launch processes
-    moved_main = float(ab["moved_leaf"] + ab["moved_internal"])   # what one pass over the targets moves, however many seeds ride on it
-    # Counters of the same kernels from the rocprofv3 PMC passes kept under profiles/ (rocprofv3 cannot run inside this process;
-    # tools/profile_round.sh + tools/profile_collect.py -> profiles/traffic.json, used only while the hash of the sweep kernels'
-    # sources recorded there still matches - counters read from other kernel sources say nothing: null):
-    #   HBM bytes per launch = FETCH_SIZE x 2 (gfx950 correction, MI355X_MICROARCH.md "HBM") + WRITE_SIZE
-    #   VALU instructions per launch = SQ_INSTS_VALU (wavefront instructions; x 64 lanes)
-    traffic = None
-    pmc = {}
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath) and (n, L, world) == (1000000, 200, 1):
-        t = json.load(open(tpath))
-        if t.get("kernel_sources_sha256") == sweep_kernel_hash():
-            pmc = t.get("sweep_launch_average", {})
-            traffic = pmc.get("bytes_per_launch")
-    # peak VALU issue: 256 CUs x 4 SIMDs x 16 lanes per cycle x 2.4 GHz (MI355X_MICROARCH.md) = 3.93e13 lane-instructions/s
-    VALU_PEAK = 256 * 64 * 2.4e9
-
-    def per_kind(ms, nl, ns, key):
-        spl = ns / max(nl, 1)
-        rec = pmc.get(key, {})
-        out = dict(avg_launch_ms=ms, sweeps_per_launch=spl,
-                   algorithmic_equiv_gbs=alg_sweep * spl / (ms * 1e-3) / 1e9 if ms > 0 else 0.0,
-                   moved_model_gbs=moved_main / (ms * 1e-3) / 1e9 if ms > 0 else 0.0)
-        if rec.get("bytes_per_launch") and ms > 0:
-            out["hbm_bytes_per_launch_pmc"] = int(rec["bytes_per_launch"])
-            out["hbm_frac_physical"] = rec["bytes_per_launch"] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-        if rec.get("valu_wave_insts_per_launch") and ms > 0:
-            out["valu_lane_insts_per_launch"] = int(rec["valu_wave_insts_per_launch"] * 64)
-            out["valu_frac"] = rec["valu_wave_insts_per_launch"] * 64 / (ms * 1e-3) / VALU_PEAK
-            if rec.get("valu_busy_frac_pmc") is not None:
-                out["valu_busy_frac_pmc"] = rec["valu_busy_frac_pmc"]
-        return out
-
-    # `achieved` / `frac` price what the memory system SEES: the bytes one launch moves (the PMC figure while it belongs to these
-    # kernel sources, else the layout model of workload.py) / the launch's duration - never above the peak.  With S seeds sharing a
-    # pass (vft_sweep_batch) the algorithm's own byte count, SURVEY 8(d)'s per-sweep figure x the sweeps a launch carries, is an
-    # EQUIVALENT rate only (`algorithmic_equiv_gbs`: what a seed-by-seed stream would have to sustain) and is not divided by the peak.
-    phys = float(traffic) if traffic else moved_main
-    achieved = phys / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
-    valu = None
-    if pmc.get("valu_wave_insts_per_launch") and kern_ms > 0:
-        li = pmc["valu_wave_insts_per_launch"] * 64.0
-        valu = dict(lane_insts_per_launch=int(li), achieved_lane_insts_per_s=li / (kern_ms * 1e-3), peak_lane_insts_per_s=VALU_PEAK,
-                    frac=li / (kern_ms * 1e-3) / VALU_PEAK, source="profiles/traffic.json (rocprofv3 --pmc SQ_INSTS_VALU)")
-    roofline = dict(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
-                    traffic=traffic, bytes_source="pmc" if traffic else "layout_model",
-                    limited_by="valu (instruction issue: S seeds share one pass over the targets, the stream is read once per S sweeps)",
-                    valu=valu,
-                    kernel="k_sweep_nt_profq_multi<float,4> (four profile seeds per launch) / k_sweep_nt_leafq_multi<float,4> (four leaf seeds per launch)",
-                    launches=int(launches), sweeps=int(sweeps), sweeps_per_launch=sweeps_per_launch, avg_launch_ms=kern_ms,
-                    algorithmic_bytes_per_sweep=int(alg_sweep), algorithmic_bytes_per_launch=int(alg_main),
-                    algorithmic_equiv_gbs=alg_main / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0,
-                    moved_bytes_per_launch_model=int(moved_main),
-                    phi=ab["phi"],
-                    profile_seed_launch=per_kind(prof_ms, n_prof_launches, n_prof_sweeps, "profile_seed_instance") if not use_dist else None,
-                    leaf_seed_launch=per_kind(leaf_ms, n_leaf_launches, n_leaf_sweeps, "leaf_seed_instance") if not use_dist else None,
-                    step=dict(algorithmic_bytes=int(alg_sweep * len(seeds)), algorithmic_equiv_gbs=alg_sweep * len(seeds) / (elapsed / args.steps) / 1e9))
-    assert roofline["frac"] <= 1.0, "a physical fraction above the peak: the byte count is wrong"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
 
     line = dict(metric="profile-ops/sec", value=value, unit="profile-ops/s", n_gpus=world, steps=args.steps,
                 warmup=args.warmup, ms_per_step=1e3 * elapsed / args.steps, higher_is_better=True,
@@ -692,8 +729,9 @@ def main():
                 config=dict(workload="c4_1M_x200_nt_tophits" if (n, L) == (1000000, 200) else "custom_tophits",
                             n_seqs=n, n_pos=L, internal_profiles=n_join, active_nodes=int(state.n_active),
                             seeds_per_step=len(seeds), top_k=k, sharding="target-range x%d" % world,
-                            setup_s=round(setup_s, 1)),
-                roofline=roofline)
+                            setup_s=round(setup_s, 1)))
+    if args.full:
+        line["roofline"] = step_roofline(args, ops, state, seeds, k, lo, hi, world, elapsed, use_dist, one_step)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:   # reported at N = 1 only (the other ranks would wait for it)
         line["cpu_baseline"] = cpu_baseline(state, codes, ops)
     elif rank == 0:

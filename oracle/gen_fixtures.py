@@ -575,6 +575,35 @@ def gen_c2(tmp):
     print("bb_c2_crc: %d bytes of Newick, crc %d, %d TreeLogLk lines, %.0f s" % (len(tree), zlib.crc32(tree.encode()), len(ll), wall))
 
 
+def gen_c2_threads(tmp, threads=64):
+    """Config C2's alignment under Jukes-Cantor (`-gtr` is not reproducible in the reference at T > 1) on the schedule of a T-thread run:
+    `VeryFastTree -nt -threads T -seed 1`, the complete default pipeline with SH-like supports - the printed tree and the TreeLogLk lines
+    this backend returns (the ML NNI rounds and ML_Lengths2), for tests/test_gpu_fullsize.py (thr_c2_10k_t64.npz)."""
+    import time
+    codes = synth.random_descent_codes(10000, 1000, 4, 0.03, 0.01, seed=2)
+    fa, log = os.path.join(tmp, "c2t.fa"), os.path.join(tmp, "c2t.log")
+    synth.codes_to_fasta(codes, fa, synth.ALPHABET_NT)
+    del codes
+    flags = ["-nt", "-threads", str(threads), "-seed", "1"]
+    t0 = time.time()
+    res = subprocess.run([REFBIN] + flags + ["-log", log, fa], check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                         env=dict(os.environ, OMP_WAIT_POLICY="passive"))
+    save_c2_threads(res.stdout, open(log).read(), flags, threads, time.time() - t0)
+
+
+def save_c2_threads(stdout, log_text, flags, threads, wall):
+    ll = [float(m.group(1)) for m in re.finditer(r"^TreeLogLk\tML_NNI\d+\t(\S+)", log_text, re.M)]
+    m2 = re.search(r"^TreeLogLk\tML_Lengths2\t(\S+)", log_text, re.M)
+    if m2:
+        ll.append(float(m2.group(1)))
+    name = "thr_c2_10k_t%d" % threads
+    np.savez_compressed(os.path.join(GOLDEN, name + ".npz"), newick=np.frombuffer(stdout, dtype=np.uint8), loglk=np.array(ll),
+                        threads=np.int64(threads), flags=np.frombuffer(" ".join(flags).encode(), dtype=np.uint8),
+                        alignment=np.frombuffer(b"random_descent_codes(10000, 1000, 4, 0.03, 0.01, seed=2)", dtype=np.uint8),
+                        reference_wall_s=np.float64(wall))
+    print("%s: %d bytes of Newick, %d TreeLogLk lines, %.0f s" % (name, len(stdout), len(ll), wall))
+
+
 C5_PARAMS = {
     # tag prefix -> (mu, gap, seed): "c5" is SURVEY.md 8(d)'s config C5; "c5mu03" are rounds 4-5's fixtures, made on C2's generator
     # parameters by mistake (less divergence, half the gaps) and kept as extra cases
@@ -834,6 +863,8 @@ def main():
             gen_c3_full(tmp)
         if "c2" in which:   # not part of the default set: minutes
             gen_c2(tmp)
+        if "c2_threads" in which:   # not part of the default set: minutes on a few dozen cores
+            gen_c2_threads(tmp)
         for w in which:     # `c5:<n>`: config C5's generator at n sequences (50000 = the config itself, hours); `c5h:<n>` harvests a finished run
             if w.startswith("c5:"):
                 gen_c5(tmp, int(w[3:]))

@@ -43,14 +43,14 @@ def test_a_failing_rank_fails_the_launcher():
 
 
 def test_single_gpu_launcher_merges_its_children_and_survives_a_dying_leg():
-    """At N = 1 bench.py is a launcher that never touches the GPU: the step measurement and every end-to-end leg are child processes,
+    """At N = 1 `bench.py --full` is a launcher that never touches the GPU: the step measurement and every end-to-end leg are child processes,
     their records are merged into one line, and a leg whose process dies (here: killed by the test hook) costs its own record only.
     The line is printed after the step measurement and again after every leg, each a superset of the one before (whatever ends the
     launcher early, what was measured by then is on stdout): the last line is the result."""
     env = dict(os.environ, VFT_BENCH_FAKE_CHILD="e2e_c2_threads")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-e2e-c5-one-thread"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-e2e-c5-one-thread"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     lines = [json.loads(ln) for ln in res.stdout.decode().splitlines() if ln.startswith("{")]
     legs = ["e2e", "e2e_c4", "e2e_c2", "e2e_c2_threads", "e2e_c5_threads", "e2e_c4s_threads", "e2e_c4_full_threads"]
@@ -70,7 +70,7 @@ def test_a_leg_that_would_pass_the_time_budget_is_skipped_not_started():
     env = dict(os.environ, VFT_BENCH_FAKE_CHILD="none")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--time-budget", "200"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--time-budget", "200"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     line = [json.loads(ln) for ln in res.stdout.decode().splitlines() if ln.startswith("{")][-1]
     assert "skipped" in line["e2e_c4_full_threads"] and "skipped" in line["e2e_c5"]

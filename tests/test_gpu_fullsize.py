@@ -306,20 +306,20 @@ def test_c5_generator_tree_equals_the_reference_tree(fixture, mu, gap, seed):
 def test_c2_shape_on_the_64_thread_schedule_equals_the_reference_run():
     """10 000 nt x 1 000 under Jukes-Cantor (config C2's shape; `-gtr` is not reproducible in the reference at T > 1) on the schedule of
     a 64-thread run: this backend (threads = 64: the walks of the reference's tree partitions in lockstep, host/MLLengths.h) against
-    the compiled reference run HERE with `-threads 64` - the printed trees, SH supports included, byte for byte.  Needs oracle/_ref
-    (travels with the snapshot) and a box with a few dozen cores; about 1.5 minutes."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.exists(os.path.join(root, "oracle", "_ref", "VeryFastTree")):
-        pytest.skip("the compiled reference is not on this box")
-    if (os.cpu_count() or 1) < 16:
-        pytest.skip("too few cores for a 64-thread run of the reference")
-    out = subprocess.run([sys.executable, os.path.join(root, "tests", "compare_with_reference_run.py"), "10000", "1000", "--threads", "64"],
-                         check=True, stdout=subprocess.PIPE, timeout=1200).stdout.decode()
-    print(out)
-    assert "byte-identical output: YES" in out
+    the compiled reference's `-threads 64` run of the same alignment (tests/golden/thr_c2_10k_t64.npz, oracle/gen_fixtures.py
+    c2_threads) - the printed trees, SH supports included, byte for byte."""
+    import golden_util as G
+    from veryfasttree_amd import HipProfileOps, synth
+    from veryfasttree_amd.backend import nj_newick
+    ref = G.load("thr_c2_10k_t64")
+    assert bytes(ref["alignment"]).decode() == "random_descent_codes(10000, 1000, 4, 0.03, 0.01, seed=2)" and int(ref["threads"]) == 64
+    codes = synth.random_descent_codes(10000, 1000, 4, 0.03, 0.01, seed=2)
+    names = ["s%d" % k for k in range(len(codes))]
+    tree, loglk = nj_newick(lambda m, Lp: HipProfileOps(m, Lp, 4, np.float32, max_nodes=3 * m), codes, names, dtype=np.float32,
+                            me_lengths=True, me_nni=True, spr=2, ml_nni=20, n_bootstrap=1000, return_loglk=True, threads=64,
+                            second_level=False)
+    print("TreeLogLk", list(loglk), "reference", list(ref["loglk"]))
+    assert tree == bytes(ref["newick"]).decode().strip()
 
 
 @pytest.mark.parametrize("n,L,seed,mu,gap", [(100000, 500, 3, 0.03, 0.01), (1000000, 200, 4, 0.02, 0.01)])

@@ -33,14 +33,14 @@ def pmc_avg(csv_path):
 for f in ("bench_line.json", "bench_line_under_rocprof.json"):
     shutil.copy(os.path.join(src, f), os.path.join(dst, "%s_%s" % (name, f)))
 stats_txt(os.path.join(src, "bench_kernel_stats.csv"), os.path.join(dst, name + "_bench_kernel_stats.txt"),
-          "python3 bench.py --steps 10 --warmup 2 --no-e2e --no-cpu-baseline (1 x MI355X)")
+          "python3 bench.py --full --steps 10 --warmup 2 --no-e2e --no-cpu-baseline (1 x MI355X)")
 for a in ("nt", "aa"):
     shutil.copy(os.path.join(src, "ops_table_%s.txt" % a), os.path.join(dst, "%s_ops_table_%s.txt" % (name, a)))
     stats_txt(os.path.join(src, "ops_%s_kernel_stats.csv" % a), os.path.join(dst, "%s_ops_%s_kernel_stats.txt" % (name, a)),
               "python3 tools/bench_ops.py %s (1 x MI355X)" % a)
 fetch, write = pmc_avg(os.path.join(src, "bench_pmc_fetch.csv")), pmc_avg(os.path.join(src, "bench_pmc_write.csv"))
 with open(os.path.join(dst, name + "_bench_pmc.txt"), "w") as f:
-    f.write("# python3 bench.py --steps 3 --warmup 1 --no-e2e --no-dense --no-cpu-baseline, two rocprofv3 passes:\n"
+    f.write("# python3 bench.py --full --steps 3 --warmup 1 --no-e2e --no-dense --no-cpu-baseline, two rocprofv3 passes:\n"
             "# --pmc FETCH_SIZE and --pmc WRITE_SIZE (KB per dispatch, averaged per kernel)\n")
     f.write("%-110s %-11s %7s %16s %12s\n" % ("kernel", "counter", "calls", "avg_value_kb", "avg_ns"))
     for table in (fetch, write):
@@ -54,7 +54,7 @@ valu = pmc_avg(os.path.join(src, "bench_pmc_valu.csv")) if os.path.exists(os.pat
 mix = pmc_avg(os.path.join(src, "bench_pmc_mix.csv")) if os.path.exists(os.path.join(src, "bench_pmc_mix.csv")) else {}
 if valu:
     with open(os.path.join(dst, name + "_bench_pmc_valu.txt"), "w") as f:
-        f.write("# python3 bench.py --steps 3 --warmup 1 --no-e2e --no-dense --no-cpu-baseline under rocprofv3 --pmc, two passes:\n"
+        f.write("# python3 bench.py --full --steps 3 --warmup 1 --no-e2e --no-dense --no-cpu-baseline under rocprofv3 --pmc, two passes:\n"
                 "# SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY\n"
                 "# GRBM_GUI_ACTIVE SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS\n"
                 "# (averages per dispatch; SQ_ACTIVE_* / SQ_WAVE_CYCLES / SQ_WAIT_* count quad-cycles summed over the wavefronts;\n"
