@@ -335,6 +335,34 @@ int vft_leaf_block_distances(vft_ctx *ctx, int64_t n_a, const int64_t *a, int64_
    (NJ.tcc:3110-3120) and every ME-phase distance are this call. */
 int vft_profile_distances(vft_ctx *ctx, int64_t n, const int64_t *i, const int64_t *j, void *dist, void *weight);
 
+/* ---- exhaustive neighbour joining (`-slow`: exhaustiveNJSearch, NJ.tcc:3648-3684, dispatch :2857-2870)
+ * The reference recomputes setDistCriterion for every pair of active nodes at every join.  The join distance of two
+ * unchanged nodes does not change between joins, only the out-distances in the criterion do, so this backend keeps the
+ * distances: a device-resident n_seqs x n_seqs matrix of numeric_t (both triangles; csrc/vft_kernels_exhaustive.h), filled
+ * once, given one new row per join, and searched once per join. */
+typedef struct { int32_t i, j; double dist, criterion; } vft_exhaustive_best_t;   /* i < j: node ids */
+/* allocates the matrix (n_seqs * roundup(n_seqs, 64) numbers of the context's precision); VFT_ERR_HIP with the size in the
+   message when the device cannot hold it.  vft_destroy releases it too. */
+int vft_exhaustive_create(vft_ctx *ctx);
+int vft_exhaustive_destroy(vft_ctx *ctx);
+/* every leaf x leaf join distance (seqDist, NJ.tcc:1601-1624, through setDistCriterion :1115-1124), computed on the device
+   into the matrix; all leaves must still be active.  Stream-ordered. */
+int vft_exhaustive_fill(vft_ctx *ctx);
+/* after the join of i and j into newnode (vft_join_fused): the distances (v, newnode) of every active node v - profileDist
+   with newnode as profile2, the order of the reference's loop (:3662-3670; codeDist comes from profile2, :1178-1180), minus
+   the diameters - replace what the matrix held for i; j's place goes to the node stored last.  Stream-ordered. */
+int vft_exhaustive_join(vft_ctx *ctx, int64_t i, int64_t j, int64_t newnode);
+/* exhaustiveNJSearch: the pair of active nodes with the lowest criterion (setCriterion, NJ.tcc:1099-1107, on the stored
+   distance and the two out-distances), ties to the lexicographically first (i, j) - the reference's choice at one thread
+   (strict <, i ascending, j > i ascending).  n_active must be the number of nodes the matrix holds, and every active node's
+   out-distance must carry the stamp n_active (vft_out_distances(ctx, 0, NULL, n_active, totdiam)): VFT_ERR_STATE otherwise.
+   Waits for the result. */
+int vft_exhaustive_search(vft_ctx *ctx, int64_t n_active, vft_exhaustive_best_t *out);
+/* Tests and tools: the matrix row of `node` - n_live = the number of nodes held, nodes[n_live] = their ids in storage
+   order, dist[n_live] = the stored distance of (node, nodes[k]) (numeric_t, host; the entry of the node itself is
+   unspecified).  nodes / dist may be NULL.  Waits. */
+int vft_exhaustive_row(vft_ctx *ctx, int64_t node, int64_t *n_live, int64_t *nodes, void *dist);
+
 /* ---- likelihood (ML phase)
  * pairLogLk (NJ.tcc:1192-1447) for n independent pairs; site_lk (n x n_pos doubles, host) may be NULL, when
  * given it receives the per-site likelihoods lkAB (what the reference multiplies into site_likelihoods[]).

@@ -103,7 +103,15 @@ typedef struct {
                                    vector_add, NJ.tcc:763-783) this rounds differently from the one-thread order - the join order may
                                    differ from the one-thread reference's in the last bits' wake - but it depends on P only: the same tree
                                    on 1, 2, 4 or 8 ranks. */
-    int32_t pad_;
+    int32_t slow;               /* `-slow` (exhaustiveNJSearch, NJ.tcc:3648-3684; VeryFastTree.cpp:113-115 turns top hits off): every join
+                                   takes the pair of active nodes with the lowest criterion, ties to the first (i, j) - the reference's
+                                   choice at one thread - found on a device-resident matrix of join distances (vft_exhaustive_* in
+                                   vft_hip.h) that gets one new row per join.  tophits_mult is ignored; with fastest it is an error
+                                   (VeryFastTree.cpp:109-111).  The root, the minimum-evolution lengths, the local supports and mllen
+                                   do not read the option: `-slow -noml -nome [-nosupport]` and `-slow -nome -mllen` come out byte for
+                                   byte.  Not built: -slow with me_nni, spr or ml_nni (the reference's updateForNNI, SPR and DoNNI
+                                   behave differently under -slow, NJ.tcc:1883-1901, :6267-6284, :5980) and with a vft_comm of more
+                                   than one rank - each an error, never the non-slow stage.  0 = everything above as before. */
 } vft_nj_options;
 #define VFT_NJ_DEBUG_HOST_JOINS 1
 #define VFT_NJ_DEBUG_HOST_LISTS 2

@@ -3,6 +3,7 @@
 or - with -mllen - the tree of `VeryFastTree -nt -nome -mllen [-nocat | -cat N] [-nosupport]` (Jukes-Cantor).
 
     python tools/nj_tree.py in.fasta [-fastest] [-double] [-nosupport] [-nj-lengths] [-mllen [-nocat | -cat N]] > tree.nwk
+    python tools/nj_tree.py in.fasta -slow [-double] [-nosupport] [-nj-lengths] [-mllen [-nocat | -cat N]] > tree.nwk   # `VeryFastTree -slow ...`
     python tools/nj_tree.py in.fasta -full [-gtr] [-double] [-nosupport] > tree.nwk     # what plain `VeryFastTree -nt [-gtr]` prints
     python tools/nj_tree.py in.fasta -full -lg -double > tree.nwk     # proteins: `VeryFastTree -lg -double-precision` (-aa / -jtt, -wag, -lg)
     python tools/nj_tree.py in.fasta -full -threads 64 [-gamma] [-spr N] > tree.nwk   # the schedule of `VeryFastTree -threads 64`; -gamma; -spr N rounds
@@ -12,6 +13,9 @@ lengths (updateBranchLengths), local-bootstrap supports (1000 resamples, reliabi
 the NJ branch lengths and prints no supports (the reference's "NJ" log line).  -mllen: maximum-likelihood branch
 lengths on that topology (optimizeAllBranchLengths rounds, CAT rate categories unless -nocat) and SH-like supports
 (testSplitsML, 1000 resamples) unless -nosupport; the TreeLogLk of every round goes to stderr.
+-slow: the exhaustive search of the reference's `-slow` (every join is the best pair of all active nodes, on a distance
+matrix kept on the device) instead of top hits; not together with -fastest (as in the reference) or -full (the NNI and
+SPR stages of a -slow run are not built).
 Sequence normalisation and uniquify follow Alignment.cpp:453-526 (U -> T, '.' -> '-', duplicates by sequence string in
 first-occurrence order; N -> X for nucleotides)."""
 import os, sys
@@ -45,6 +49,11 @@ def main():
     if not args or args[0].startswith("-"):
         sys.exit(__doc__)
     fastest, double, nj_len = "-fastest" in args, "-double" in args, "-nj-lengths" in args
+    slow = "-slow" in args
+    if slow and fastest:
+        sys.exit("-slow and -fastest exclude each other")
+    if slow and "-full" in args:
+        sys.exit("-slow with -full is not built: use -slow alone (the tree of -slow -noml -nome) or with -mllen")
     mllen = 0
     if "-mllen" in args:
         mllen = 1 if "-nocat" in args else (int(args[args.index("-cat") + 1]) if "-cat" in args else 20)
@@ -90,7 +99,7 @@ def main():
         extra["aa_model"] = aa
     tree, loglk = nj_newick(lambda n, L: HipProfileOps(n, L, 20 if aa else 4, dt, max_nodes=3 * n), codes_all, names, fastest=fastest,
                             dtype=dt, me_lengths=not nj_len, unique=(np.array(unique_first, np.int64), aln_next),
-                            n_bootstrap=n_boot, mllen=mllen, return_loglk=True, **extra)
+                            n_bootstrap=n_boot, mllen=mllen, return_loglk=True, slow=slow, **extra)
     for k, ll in enumerate(loglk):
         sys.stderr.write("TreeLogLk\t%s%d\t%.4f\n" % ("Round" if extra else "Length", k + 1, ll))
     print(tree)

@@ -34,6 +34,7 @@ EXPORTS = [
     "vft_sweep_batch", "vft_sweep_batch_view", "vft_set_shard", "vft_merge_hits", "vft_merge_hits_batch", "vft_sweep_info", "vft_sweep_batch_info", "vft_sweep_results", "vft_pair_distances", "vft_pair_loglk", "vft_posterior_profiles", "vft_set_profile_rows", "vft_average_chain", "vft_average_chains", "vft_profiles_differ", "vft_get_max_nodes", "vft_get_n_codes", "vft_walk_step", "vft_walk_server_start", "vft_walk_server_stop", "vft_walk_submit", "vft_walk_submit_dual", "vft_walk_dual_choice", "vft_walk_scoredist", "vft_walk_collect", "vft_walk_server_ticks", "vft_posterior_chains_blen", "vft_ml_quartet_nni_flags", "vft_branch_lengths_set", "vft_branch_lengths_get", "vft_branch_lengths_gather", "vft_branch_lengths_scatter", "vft_posterior_profiles_blen", "vft_posterior_chain_blen", "vft_ml_optimize_splits", "vft_ml_split_tests", "vft_ml_quartet_nni", "vft_ml_eval_count",
     "vft_join_nodes", "vft_profile_distances", "vft_split_supports", "vft_timer_start", "vft_timer_stop_ms", "vft_sweep_kernel_ms", "vft_sweep_table_kernel_ms", "vft_sweep_kernel_sweeps",
     "vft_debug_log", "vft_debug_option", "vft_tophits_create", "vft_tophits_upload", "vft_tophits_download", "vft_tophits_best", "vft_tophits_join", "vft_tophits_refresh", "vft_nj_engine_create", "vft_nj_engine_set_state", "vft_nj_engine_get_state", "vft_nj_engine_visible_set", "vft_nj_engine_visible_get", "vft_nj_engine_nodes_set", "vft_nj_engine_topvisible_set", "vft_nj_engine_topvisible_get", "vft_nj_engine_reset_candidates", "vft_nj_engine_enqueue", "vft_nj_engine_poll", "vft_nj_engine_resume", "vft_nj_engine_log", "vft_nj_engine_adopt", "vft_leaf_block_distances", "vft_set_shard_mode", "vft_join_fused", "vft_block_distances", "vft_pair_distances_refresh",
+    "vft_exhaustive_create", "vft_exhaustive_destroy", "vft_exhaustive_fill", "vft_exhaustive_join", "vft_exhaustive_search", "vft_exhaustive_row",
 ]
 
 
@@ -58,7 +59,11 @@ class _NJOptions(C.Structure):
     _fields_ = [("fastest", I32), ("use_tophits_2nd", I32), ("tophits_mult", C.c_double), ("tophits_close", C.c_double),
                 ("tophits_refresh", C.c_double), ("topvisible_mult", C.c_double), ("stale_out_limit", C.c_double),
                 ("f_reset_out_profile", C.c_double), ("n_reset_out_profile", I32), ("tophits2_safety", I32),
-                ("tophits2_mult", C.c_double), ("tophits2_refresh", C.c_double), ("scoredist", I32), ("mllen", I32), ("me_nni", I32), ("ml_nni", I32), ("spr", I32), ("gtr", I32), ("aa_model", I32), ("comm", P), ("threads", I32), ("debug_flags", I32), ("gamma", I32), ("out_profile_parts", I32), ("pad_", I32)]
+                ("tophits2_mult", C.c_double), ("tophits2_refresh", C.c_double), ("scoredist", I32), ("mllen", I32), ("me_nni", I32), ("ml_nni", I32), ("spr", I32), ("gtr", I32), ("aa_model", I32), ("comm", P), ("threads", I32), ("debug_flags", I32), ("gamma", I32), ("out_profile_parts", I32), ("slow", I32)]
+
+
+class _ExhaustiveBest(C.Structure):
+    _fields_ = [("i", I32), ("j", I32), ("dist", C.c_double), ("criterion", C.c_double)]
 
 
 _lib = None
@@ -142,9 +147,10 @@ class TorchComm:
 
 
 def nj_run(ops, codes, fastest=False, max_joins=-1, tophits_refresh=None, second_level=None, scoredist=False, aa_model=None,
-           tophits_mult=1.0, comm=None, debug_flags=0, out_profile_parts=0):
+           tophits_mult=1.0, comm=None, debug_flags=0, out_profile_parts=0, slow=False):
     """fastNJ through the C++ host driver.  Returns (joins[n,3], criterion[n]).
-    second_level defaults to `fastest`, as in the reference at one thread (-fastest turns -2nd on)."""
+    second_level defaults to `fastest`, as in the reference at one thread (-fastest turns -2nd on).
+    slow: `-slow`, the exhaustive search over a device-resident distance matrix (vft_exhaustive_*)."""
     lib = load_host_library()
     codes = np.ascontiguousarray(codes, np.uint8)
     n, L = codes.shape
@@ -153,7 +159,7 @@ def nj_run(ops, codes, fastest=False, max_joins=-1, tophits_refresh=None, second
     opt = _NJOptions(1 if fastest else 0, 1 if second_level else 0, float(tophits_mult), -1.0,
                      tophits_refresh if tophits_refresh is not None else (0.5 if fastest else 0.8), 1.5, 0.01, 0.02,
                      200, 3, 1.0, 0.6, 1 if scoredist else 0, 0, 0, 0, 0, 0, AA_MODELS[aa_model],
-                     comm.pointer() if comm is not None else None, 1, int(debug_flags), 0, int(out_profile_parts), 0)
+                     comm.pointer() if comm is not None else None, 1, int(debug_flags), 0, int(out_profile_parts), 1 if slow else 0)
     joins = np.zeros((max(n - 3, 1), 3), np.int64)
     crit = np.zeros(max(n - 3, 1), np.float64)
     nj = I64(0)
@@ -246,7 +252,7 @@ def uniquify(codes):
 
 def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtype=np.float32, me_lengths=False,
               unique=None, scoredist=False, n_bootstrap=0, mllen=0, return_loglk=False, return_rates=False, me_nni=False, ml_nni=0, spr=0, gtr=False, return_gtr=False,
-              aa_model=None, comm=None, threads=1, debug_flags=0, gamma=False, out_profile_parts=0):
+              aa_model=None, comm=None, threads=1, debug_flags=0, gamma=False, out_profile_parts=0, slow=False):
     """The NJ phase of the whole alignment `codes_all` (duplicates included) as the reference's "NJ" tree string.
     make_ops(n_unique, n_pos) -> HipProfileOps for the unique sequences (max_nodes >= 3 * n_unique with me_lengths:
     then the tree carries the minimum-evolution branch lengths, the final output of -noml -nome -nosupport)."""
@@ -264,7 +270,7 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
         second_level = fastest
     opt = _NJOptions(1 if fastest else 0, 1 if second_level else 0, 1.0, -1.0, 0.5 if fastest else 0.8, 1.5, 0.01, 0.02,
                      200, 3, 1.0, 0.6, 1 if scoredist else 0, int(mllen), 1 if me_nni else 0, int(ml_nni), int(spr), 1 if gtr else 0,
-                     AA_MODELS[aa_model], comm.pointer() if comm is not None else None, int(threads), int(debug_flags), 1 if gamma else 0, int(out_profile_parts), 0)
+                     AA_MODELS[aa_model], comm.pointer() if comm is not None else None, int(threads), int(debug_flags), 1 if gamma else 0, int(out_profile_parts), 1 if slow else 0)
     blob = b"".join(nm.encode() + b"\0" for nm in names)
     cap = 64 * len(names) + len(blob) + 1024
     out = C.create_string_buffer(cap)
@@ -459,6 +465,30 @@ class HipProfileOps:
         """joinNodes + averageProfile(newnode, i, j) + its self-distance + updateOutProfile in one launch (vft_join_fused)."""
         self._chk(self.lib.vft_join_fused(self.ctx, I64(i), I64(j), I64(newnode), C.c_double(diameter), I64(stale_stamp),
                                           I64(n_active_old), C.c_int32(1 if update_out_profile else 0)))
+
+    # ---- exhaustive NJ (`-slow`): the device-resident distance matrix (vft_exhaustive_*)
+    def exhaustive_create(self):
+        self._chk(self.lib.vft_exhaustive_create(self.ctx))
+
+    def exhaustive_fill(self):
+        self._chk(self.lib.vft_exhaustive_fill(self.ctx))
+
+    def exhaustive_join(self, i, j, newnode):
+        self._chk(self.lib.vft_exhaustive_join(self.ctx, I64(i), I64(j), I64(newnode)))
+
+    def exhaustive_search(self, n_active):
+        """(i, j, dist, criterion) of the exhaustive search: the lowest criterion, ties to the first (i, j)"""
+        out = _ExhaustiveBest()
+        self._chk(self.lib.vft_exhaustive_search(self.ctx, I64(n_active), C.byref(out)))
+        return int(out.i), int(out.j), self.dt.type(out.dist), self.dt.type(out.criterion)
+
+    def exhaustive_row(self, node):
+        """(nodes, dist): the nodes the matrix holds, in storage order, and the stored distances of `node` against them"""
+        n = I64(0)
+        self._chk(self.lib.vft_exhaustive_row(self.ctx, I64(node), C.byref(n), None, None))
+        nodes, dist = np.zeros(n.value, np.int64), np.zeros(n.value, self.dt)
+        self._chk(self.lib.vft_exhaustive_row(self.ctx, I64(node), C.byref(n), _ptr(nodes), _ptr(dist)))
+        return nodes, dist
 
     def out_distance_mirror(self):
         """numpy views of the host-mapped mirrors of outDistances[] / nOutDistActive[] (vft_out_distance_mirror): what the

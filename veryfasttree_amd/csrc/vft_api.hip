@@ -29,6 +29,7 @@ VFT_ML_LONG_INSTANCES(extern)    // compiled in vft_ml_kernels_long.hip
 #include "vft_kernels_tophits.h"
 #include "vft_kernels_njengine.h"
 #include "vft_kernels_walk.h"
+#include "vft_kernels_exhaustive.h"
 
 VFT_WALK_SERVER_INSTANCES(extern)   // compiled in vft_walk_kernels.hip
 
@@ -195,6 +196,14 @@ struct vft_ctx {
     int32_t *njSlotI = nullptr, *njCandI = nullptr;
     void *njSlotR = nullptr, *njCandR = nullptr;
     int njTopPad = 0, njCapPad = 0;
+    // exhaustive NJ (vft_kernels_exhaustive.h): the slot-space matrix of join distances and what a search reads beside it
+    void *exM = nullptr, *exSlotOut = nullptr, *exPart = nullptr;
+    int64_t exLd = 0, exLive = 0;        // row stride (elements); live slots are 0 .. exLive-1, exLive = 0: not filled
+    int64_t *exNodeOf = nullptr;         // [exLd]: node of a slot, -1 = free
+    int32_t *exSlotNode = nullptr;
+    unsigned int *exStale = nullptr;
+    std::vector<int64_t> exNodeOfH;      // host copies
+    std::vector<int32_t> exSlotOfH;      // [max_nodes]
     // timing
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<hipEvent_t> kev;
@@ -625,6 +634,7 @@ extern "C" int vft_destroy(vft_ctx *c) {
         hipHostFree(c->ws.hRes);
         hipFree(c->ws.dFlags);
     }
+    (void) vft_exhaustive_destroy(c);
     if (c->blen) hipFree(c->blen);
     if (c->mlLongWs) hipFree(c->mlLongWs);
     if (c->opHist) hipFree(c->opHist);
@@ -2657,9 +2667,10 @@ static int pair_distances(vft_ctx *c, int64_t n, const int64_t *pi, const int64_
 
 // the cross product of two id lists in device memory -> dist[nA][nB] (device): lane per pair for 4-state alphabets without a
 // distance matrix (k_pairs_block_tiled), a wavefront per pair otherwise
-static int launch_pairs_block(vft_ctx *c, const int64_t *dA, int64_t nA, const int64_t *dB, int64_t nB, void *dOut) {
+// (tiled = false: the wave-per-pair kernel at any alphabet - a block one node wide gives the lane-per-pair kernel one lane per workgroup)
+static int launch_pairs_block(vft_ctx *c, const int64_t *dA, int64_t nA, const int64_t *dB, int64_t nB, void *dOut, bool tiled = true) {
     const size_t tiledLds = (size_t) VFT_PB_A * (size_t) c->d.nPos * (5 * c->rs + 4) + 64;   // [A][nPos] x (4 frequencies + weight + code)
-    if (c->cfg.n_codes == 4 && !c->hasDm && tiledLds <= (144u << 10)) {
+    if (tiled && c->cfg.n_codes == 4 && !c->hasDm && tiledLds <= (144u << 10)) {
         if (tiledLds > (48u << 10) && tiledLds > c->pbLdsSet) {
             if (c->rs == 4) HIPCHK(c, hipFuncSetAttribute((const void *) k_pairs_block_tiled<float, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) tiledLds));
             else HIPCHK(c, hipFuncSetAttribute((const void *) k_pairs_block_tiled<double, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) tiledLds));
@@ -2799,6 +2810,155 @@ extern "C" int vft_leaf_block_distances(vft_ctx *c, int64_t nA, const int64_t *a
     HIPCHK(c, hipMemcpyAsync(weight, o + oB, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(crit, o + 2 * oB, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VFT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- exhaustive NJ (-slow)
+extern "C" int vft_exhaustive_destroy(vft_ctx *c) {
+    if (!c) return VFT_ERR_INVALID;
+    if (c->exM) (void) hipStreamSynchronize(c->stream);
+    void *dev[] = {c->exM, c->exSlotOut, c->exPart, c->exNodeOf, c->exSlotNode, c->exStale};
+    for (void *p: dev)
+        if (p) hipFree(p);
+    c->exM = c->exSlotOut = c->exPart = nullptr;
+    c->exNodeOf = nullptr;
+    c->exSlotNode = nullptr;
+    c->exStale = nullptr;
+    c->exLd = c->exLive = 0;
+    return VFT_OK;
+}
+
+extern "C" int vft_exhaustive_create(vft_ctx *c) {
+    if (!c) return VFT_ERR_INVALID;
+    (void) vft_exhaustive_destroy(c);
+    const int64_t S = c->d.nSeqs, ld = (S + 63) & ~(int64_t) 63;
+    const size_t bytes = (size_t) S * (size_t) ld * c->rs;
+    if (hipMalloc(&c->exM, bytes) != hipSuccess) {
+        c->exM = nullptr;
+        (void) hipGetLastError();
+        return fail(c, VFT_ERR_HIP, "vft_exhaustive_create: no device memory for the %lld x %lld distance matrix (%zu bytes)", (long long) S,
+                    (long long) ld, bytes);
+    }
+    c->exLd = ld;
+    const size_t keyBytes = c->rs == 4 ? sizeof(ExKey<float>) : sizeof(ExKey<double>);
+    if (hipMalloc(&c->exSlotOut, (size_t) ld * c->rs) != hipSuccess || hipMalloc(&c->exPart, VFT_EX_MAX_PARTS * keyBytes) != hipSuccess ||
+        hipMalloc((void **) &c->exNodeOf, (size_t) ld * sizeof(int64_t)) != hipSuccess ||
+        hipMalloc((void **) &c->exSlotNode, (size_t) ld * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc((void **) &c->exStale, sizeof(unsigned int)) != hipSuccess) {
+        (void) hipGetLastError();
+        (void) vft_exhaustive_destroy(c);
+        return fail(c, VFT_ERR_HIP, "vft_exhaustive_create: no device memory for the slot arrays of %lld sequences", (long long) S);
+    }
+    HIPCHK(c, hipMemsetAsync(c->exStale, 0, sizeof(unsigned int), c->stream));
+    return VFT_OK;
+}
+
+extern "C" int vft_exhaustive_fill(vft_ctx *c) {
+    if (!c) return VFT_ERR_INVALID;
+    if (!c->exM) return fail(c, VFT_ERR_STATE, "vft_exhaustive_fill before vft_exhaustive_create");
+    if (!c->leavesUp) return fail(c, VFT_ERR_STATE, "vft_exhaustive_fill before vft_upload_leaves");
+    const int64_t S = c->d.nSeqs, ld = c->exLd;
+    for (int64_t v = 0; v < S; v++)
+        if (c->hParent[(size_t) v] >= 0) return fail(c, VFT_ERR_STATE, "vft_exhaustive_fill: leaf %lld has been joined already", (long long) v);
+    c->exNodeOfH.assign((size_t) ld, -1);
+    c->exSlotOfH.assign((size_t) c->d.maxNodes, -1);
+    for (int64_t v = 0; v < S; v++) {
+        c->exNodeOfH[(size_t) v] = v;
+        c->exSlotOfH[(size_t) v] = (int32_t) v;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->exNodeOf, c->exNodeOfH.data(), (size_t) ld * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
+    // M[a * ld + b] for every pair of leaves (the ids of the padding columns are -1: skipped), then lower <- upper
+    if (int r = launch_pairs_block(c, c->exNodeOf, S, c->exNodeOf, ld, c->exM)) return r;
+    const dim3 grid(cdiv(S, VFT_EX_WG), (unsigned) std::min<int64_t>(S, 32768));
+    if (c->rs == 4) launch((k_ex_mirror<float>), grid, dim3(VFT_EX_WG), 0, c->stream, (float *) c->exM, ld, S);
+    else launch((k_ex_mirror<double>), grid, dim3(VFT_EX_WG), 0, c->stream, (double *) c->exM, ld, S);
+    LAUNCHCHK(c);
+    c->exLive = S;
+    return VFT_OK;
+}
+
+extern "C" int vft_exhaustive_join(vft_ctx *c, int64_t i, int64_t j, int64_t newnode) {
+    if (!c) return VFT_ERR_INVALID;
+    if (!c->exM || c->exLive < 2) return fail(c, VFT_ERR_STATE, "vft_exhaustive_join before vft_exhaustive_fill");
+    if (i < 0 || j < 0 || i == j || i >= c->maxnode || j >= c->maxnode || newnode < c->d.nSeqs || newnode >= c->maxnode)
+        return fail(c, VFT_ERR_INVALID, "vft_exhaustive_join: bad node ids");
+    const int64_t sI = c->exSlotOfH[(size_t) i], sJ = c->exSlotOfH[(size_t) j], last = c->exLive - 1;
+    if (sI < 0 || sJ < 0 || c->exSlotOfH[(size_t) newnode] >= 0)
+        return fail(c, VFT_ERR_STATE, "vft_exhaustive_join: %lld and %lld must own slots and %lld none", (long long) i, (long long) j, (long long) newnode);
+    if (c->hParent[(size_t) i] != newnode || c->hParent[(size_t) j] != newnode)
+        return fail(c, VFT_ERR_STATE, "vft_exhaustive_join: join the nodes first (vft_join_fused)");
+    // host bookkeeping, as k_ex_move does it
+    c->exSlotOfH[(size_t) i] = c->exSlotOfH[(size_t) j] = -1;
+    c->exNodeOfH[(size_t) sI] = newnode;
+    c->exSlotOfH[(size_t) newnode] = (int32_t) sI;
+    if (sJ != last) {
+        const int64_t moved = c->exNodeOfH[(size_t) last];
+        c->exNodeOfH[(size_t) sJ] = moved;
+        c->exSlotOfH[(size_t) moved] = (int32_t) sJ;
+    }
+    c->exNodeOfH[(size_t) last] = -1;
+    c->exLive = last;
+    const int64_t n = c->exLive, sNew = c->exSlotOfH[(size_t) newnode], ld = c->exLd;
+    const dim3 g(cdiv(last + 1, VFT_EX_WG)), b(VFT_EX_WG);
+    if (c->rs == 4) launch((k_ex_move<float>), g, b, 0, c->stream, (float *) c->exM, ld, c->exNodeOf, sI, sJ, last, newnode);
+    else launch((k_ex_move<double>), g, b, 0, c->stream, (double *) c->exM, ld, c->exNodeOf, sI, sJ, last, newnode);
+    LAUNCHCHK(c);
+    // (active node, new node) for every live slot, the new node second, straight into the new node's row
+    if (int r = launch_pairs_block(c, c->exNodeOf, n, c->exNodeOf + sNew, 1, (char *) c->exM + (size_t) sNew * (size_t) ld * c->rs, false)) return r;
+    if (c->rs == 4) launch((k_ex_column<float>), dim3(cdiv(n, VFT_EX_WG)), b, 0, c->stream, (float *) c->exM, ld, sNew, n);
+    else launch((k_ex_column<double>), dim3(cdiv(n, VFT_EX_WG)), b, 0, c->stream, (double *) c->exM, ld, sNew, n);
+    LAUNCHCHK(c);
+    return VFT_OK;
+}
+
+template <typename REAL>
+static int exhaustive_search(vft_ctx *c, int64_t nActive, ExBestOut *dOut, unsigned long long seq) {
+    // a pair of rows (n columns) as 8 items once the rows are long enough: ~10 items per wavefront of a full grid at 20 000 nodes
+    const int64_t n = c->exLive, pairs = (n - 2) / 2 + 1;
+    const int H = n >= 4096 ? 8 : 1;
+    const unsigned grid = (unsigned) std::min<int64_t>(cdiv(pairs * H, VFT_EX_WG / 64), VFT_EX_MAX_PARTS);
+    launch((k_ex_prepare<REAL>), dim3(cdiv(n, VFT_EX_WG)), dim3(VFT_EX_WG), 0, c->stream, arena<REAL>(c), (const int64_t *) c->exNodeOf, n,
+           nActive, (REAL *) c->exSlotOut, c->exSlotNode, c->exStale);
+    launch((k_ex_search<REAL>), dim3(grid), dim3(VFT_EX_WG), 0, c->stream, (const REAL *) c->exM, c->exLd, n, nActive, H,
+           (const REAL *) c->exSlotOut, (const int32_t *) c->exSlotNode, (ExKey<REAL> *) c->exPart);
+    launch((k_ex_finish<REAL>), dim3(1), dim3(VFT_EX_WG), 0, c->stream, (const ExKey<REAL> *) c->exPart, (int) grid, c->exStale, dOut,
+           c->dFlag, seq);
+    LAUNCHCHK(c);
+    return VFT_OK;
+}
+
+extern "C" int vft_exhaustive_search(vft_ctx *c, int64_t nActive, vft_exhaustive_best_t *out) {
+    if (!c || !out) return VFT_ERR_INVALID;
+    if (!c->exM || c->exLive < 2) return fail(c, VFT_ERR_STATE, "vft_exhaustive_search before vft_exhaustive_fill");
+    if (nActive != c->exLive || nActive < 3)
+        return fail(c, VFT_ERR_INVALID, "vft_exhaustive_search: n_active is %lld, the matrix holds %lld nodes", (long long) nActive, (long long) c->exLive);
+    char *h, *d;
+    if (int r = io_alloc(c, sizeof(ExBestOut), &h, &d)) return r;
+    const unsigned long long seq = ++c->signalSeq;
+    if (int r = c->rs == 4 ? exhaustive_search<float>(c, nActive, (ExBestOut *) d, seq) : exhaustive_search<double>(c, nActive, (ExBestOut *) d, seq))
+        return r;
+    if (int r = wait_flag(c, seq)) return r;
+    const ExBestOut *o = (const ExBestOut *) h;
+    if (o->stale)
+        return fail(c, VFT_ERR_STATE, "vft_exhaustive_search: out-distances are not current for n_active = %lld (vft_out_distances first)", (long long) nActive);
+    out->i = o->i;
+    out->j = o->j;
+    out->dist = o->dist;
+    out->criterion = o->crit;
+    return VFT_OK;
+}
+
+extern "C" int vft_exhaustive_row(vft_ctx *c, int64_t node, int64_t *nLive, int64_t *nodes, void *dist) {
+    if (!c || !nLive) return VFT_ERR_INVALID;
+    if (!c->exM || c->exLive < 1) return fail(c, VFT_ERR_STATE, "vft_exhaustive_row before vft_exhaustive_fill");
+    if (node < 0 || node >= c->d.maxNodes || c->exSlotOfH[(size_t) node] < 0) return fail(c, VFT_ERR_INVALID, "vft_exhaustive_row: node %lld owns no slot", (long long) node);
+    *nLive = c->exLive;
+    if (nodes) memcpy(nodes, c->exNodeOfH.data(), (size_t) c->exLive * sizeof(int64_t));
+    if (dist) {
+        const char *row = (const char *) c->exM + (size_t) c->exSlotOfH[(size_t) node] * (size_t) c->exLd * c->rs;
+        HIPCHK(c, hipMemcpyAsync(dist, row, (size_t) c->exLive * c->rs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     return VFT_OK;
 }
 

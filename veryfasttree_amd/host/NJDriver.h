@@ -8,7 +8,9 @@
 // tests (tests/nj_driver_py.py) that also runs on the CPU oracle for debugging.
 //
 // Scope: deterministic single-thread semantics, default options, `-fastest` (with its second-level top-hit lists) and
-// `-fastest -no2nd`; no constraints, no BIONJ weighting, top-hits on (m >= 4 and 2m < nSeqs).
+// `-fastest -no2nd`; no constraints, no BIONJ weighting, top-hits on (m >= 4 and 2m < nSeqs); `-notop` and tiny inputs through
+// the visible set of every node; `-slow` (exhaustiveNJSearch, NJ.tcc:3648-3684) through a device-resident matrix of join
+// distances (vft_exhaustive_*): the NJ phase only - the NNI and SPR stages of a -slow run are not built.
 //
 // Device-side lazy state: out-distances are refreshed on the device inside sweeps / pair lists exactly when the
 // reference refreshes them (setCriterion, NJ.tcc:1092-1098).  Every refresh is also stored by the kernels into
@@ -84,6 +86,9 @@ namespace veryfasttree {
         /* measurements only: ML length rounds as one batch per tree height (MLLengths::optimizeRoundParallel) - not the
            reference's order in any of its modes */
         bool parallelLengths = false;
+        /* `-slow`: the exhaustive search (NJ.tcc:3648-3684) - no top hits (VeryFastTree.cpp:113-115), no visible set; every join is
+           the lowest criterion over all pairs of active nodes, the first (i, j) among equals (the reference at one thread) */
+        bool slow = false;
     };
 
     template<typename REAL>
@@ -148,10 +153,18 @@ namespace veryfasttree {
 
         const std::vector<Join> &run(int64_t maxJoins = -1) {
             if (nSeqs < 3) throw std::invalid_argument("NJDriver: fewer than 3 sequences");
+            if (opt.slow) {
+                if (opt.fastest) throw std::invalid_argument("NJDriver: -slow and -fastest exclude each other (VeryFastTree.cpp:109-111)");
+                if (opt.comm && opt.comm->world > 1) throw std::invalid_argument("NJDriver: -slow with several ranks is not built");
+                opt.tophitsMult = 0;   /* VeryFastTree.cpp:113-115: nDiffAllow = 0, every out-distance recomputed after a join */
+            }
             int64_t m = opt.tophitsMult > 0 ? (int64_t) (0.5 + opt.tophitsMult * std::sqrt((double) nSeqs)) : 0;
             /* NJ.tcc:2827-2834: no top hits on tiny inputs; the visible set then holds every node's best hit */
             const bool noTop = m < 4 || 2 * m >= nSeqs;
-            if (noTop) {
+            if (opt.slow) {   /* the leaf x leaf distances, once */
+                chkT("vft_exhaustive_create", [&]() { return vft_exhaustive_create(ctx); });
+                chkT("vft_exhaustive_fill", [&]() { return vft_exhaustive_fill(ctx); });
+            } else if (noTop) {
                 visibleAll.assign((size_t) maxnodes, Besthit());
                 for (int64_t v = 0; v < nSeqs; v++) visibleAll[(size_t) v] = bestHitOf(v, nSeqs, nullptr);   /* NJ.tcc:2849-2851 */
             } else {
@@ -167,11 +180,21 @@ namespace veryfasttree {
                     drain();
                     dumpVisibleState("host", dumpJoin, nActive);
                 }
-                Besthit join = noTop ? fastNJSearch(nActive) : topHitNJSearch(nActive);
+                Besthit join = opt.slow ? exhaustiveSearch(nActive) : noTop ? fastNJSearch(nActive) : topHitNJSearch(nActive);
                 /* setOutDistance(i), setOutDistance(j), setDistCriterion(join) (NJ.tcc:2897-2901) as ONE pair list of
                    length 1 with nDiffAllow = 0: the lazy refresh then fires for every stamp != nActive, i.e. it is the
                    unconditional setOutDistance, and the pair kernel follows in the same call */
-                if (!noTop && stamp(join.i) == nActive && stamp(join.j) == nActive && !checkJoins) {
+                if (opt.slow) {
+                    /* the search formed the criterion of exactly this pair from the stored distance and two current out-distances
+                       (the reference's setOutDistance(i), setOutDistance(j), setDistCriterion(join) recompute the same numbers) */
+                    if (checkJoins) {
+                        Besthit again = join;
+                        std::vector<Besthit *> one(1, &again);
+                        setDistCriterionBatch(nActive, one, 0);
+                        if (again.dist != join.dist) throw std::runtime_error("NJDriver: the stored distance of a -slow join differs from its recomputation");
+                        if (again.criterion != join.criterion) throw std::runtime_error("NJDriver: the criterion of a -slow join differs from its recomputation");
+                    }
+                } else if (!noTop && stamp(join.i) == nActive && stamp(join.j) == nActive && !checkJoins) {
                     /* both out-distances are current (the hill climbing of topHitNJSearch forced them) and join.dist is
                        the distance of exactly this pair of unchanged profiles: only the criterion's arithmetic is left */
                     criterionFresh(nActive, join);
@@ -224,7 +247,8 @@ namespace veryfasttree {
                     const REAL dd = diameter[newnode] - diameter[i] - diameter[j];
                     totdiam += dd;
                 }
-                if (noTop) visibleJoin(newnode, nActive - 1);
+                if (opt.slow) slowJoin(i, j, newnode, nActive - 1);
+                else if (noTop) visibleJoin(newnode, nActive - 1);
                 else topHitJoin(newnode, nActive - 1);
             }
             return joins;
@@ -2755,6 +2779,26 @@ namespace veryfasttree {
                     b.criterion = fromNew[(size_t) v].criterion;
                 }
             }
+        }
+
+        /* ---- -slow: exhaustiveNJSearch (NJ.tcc:3648-3684) on the device's distance matrix */
+        Besthit exhaustiveSearch(int64_t nActive) {
+            vft_exhaustive_best_t r;
+            chkT("vft_exhaustive_search", [&]() { return vft_exhaustive_search(ctx, nActive, &r); });
+            pending = false;   /* the call waited for the stream: the mirrors are current */
+            Besthit join;
+            join.i = r.i;
+            join.j = r.j;
+            join.dist = (REAL) r.dist;
+            join.criterion = (REAL) r.criterion;
+            if (join.i < 0 || join.j < 0) throw std::runtime_error("NJDriver: the exhaustive search found no pair");
+            return join;
+        }
+
+        void slowJoin(int64_t i, int64_t j, int64_t newnode, int64_t nActive) { /* NJ.tcc:3049-3055; nActive = the count after the join */
+            chkT("vft_out_distances", [&]() { return vft_out_distances(ctx, 0, nullptr, nActive, totdiam); });
+            chkT("vft_exhaustive_join", [&]() { return vft_exhaustive_join(ctx, i, j, newnode); });
+            pending = true;
         }
 
         Besthit topHitNJSearch(int64_t nActive) { /* NJ.tcc:4137-4262 */

@@ -191,6 +191,7 @@ static veryfasttree::NJOptions toOptions(const vft_nj_options *o) {
         opt.threads = o->threads > 1 ? o->threads : 1;
         opt.gamma = o->gamma != 0;
         opt.outProfileParts = o->out_profile_parts >= 2 ? o->out_profile_parts : 0;
+        opt.slow = o->slow != 0;
         if (o->debug_flags & VFT_NJ_DEBUG_HOST_JOINS) opt.deviceJoins = false;
         if (o->debug_flags & VFT_NJ_DEBUG_HOST_LISTS) opt.deviceLists = false;
         if (o->debug_flags & VFT_NJ_DEBUG_HOST_RESET) opt.deviceReset = false;
@@ -201,6 +202,16 @@ static veryfasttree::NJOptions toOptions(const vft_nj_options *o) {
         if (o->debug_flags & VFT_NJ_SHARD_LEAF_BLOCKS) opt.shardLeafBlocks = true;
     }
     return opt;
+}
+
+/* `-slow`: what is not built is refused before anything reaches the device (include/vft_host.h, vft_nj_options.slow) */
+static void checkSlow(const vft_nj_options *o) {
+    if (!o || !o->slow) return;
+    if (o->fastest) throw std::invalid_argument("-slow and -fastest exclude each other (VeryFastTree.cpp:109-111)");
+    if (o->me_nni || o->spr || o->ml_nni)
+        throw std::invalid_argument("-slow with me_nni, spr or ml_nni is not built: the reference's NNI and SPR stages behave differently under "
+                                    "-slow (NJ.tcc:1883-1901, 5980, 6267-6284); use -slow with -noml -nome or with -nome -mllen");
+    if (o->comm && o->comm->world > 1) throw std::invalid_argument("-slow with a vft_comm of more than one rank is not built");
 }
 
 template<typename REAL>
@@ -271,6 +282,7 @@ extern "C" int vft_nj_ml_newick(vft_ctx *ctx, const uint8_t *codes, int64_t nSeq
                                 int32_t ratesCap, int32_t *nRates, int32_t *ratecatOut, double *gtrOut, char *err, int32_t errLen) {
     if (!ctx || !codes || !uniqueFirst || !alnNext || !names || !outLen) return VFT_ERR_INVALID;
     try {
+        checkSlow(opt);
         std::vector<double> ll, rates;
         std::vector<int64_t> ratecat;
         const std::string t = precision == 8 ? runTree<double>(ctx, codes, nSeqs, nPos, opt, meLengths != 0, nBootstrap, uniqueFirst, alnNext, nAll, names, ll, rates, ratecat, gtrOut)
@@ -332,6 +344,7 @@ extern "C" int vft_nj_run(vft_ctx *ctx, const uint8_t *codes, int64_t nSeqs, int
                           int64_t *nJoins, char *err, int32_t errLen) {
     if (!ctx || !codes || !joins || !nJoins) return VFT_ERR_INVALID;
     try {
+        checkSlow(opt);
         *nJoins = precision == 8 ? runDriver<double>(ctx, codes, nSeqs, nPos, opt, maxJoins, joins, criterion)
                                  : runDriver<float>(ctx, codes, nSeqs, nPos, opt, maxJoins, joins, criterion);
         return VFT_OK;
