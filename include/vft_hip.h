@@ -531,7 +531,7 @@ int vft_debug_log(vft_ctx *ctx, int64_t n, const double *x, double *out);
 #define VFT_DEBUG_WALK_SERVER_STRIDE 11 /* 1: the server's six workgroups on six XCDs instead of one (placement is for speed only; tests run both) */
 #define VFT_DEBUG_POISON_SELECTION 14    /* fills the selection's candidate buffers of every slot with 0x7f bytes - what a recycled allocation holds - before the next sweep (tests: a collection that overflows must not look at entries it never stored) */
 #define VFT_DEBUG_ML_LONG 16            /* value != 0: the ML line searches (vft_ml_optimize_splits, vft_ml_quartet_nni*, vft_ml_split_tests) run the workspace kernels of alignments beyond 2 048 columns at any length (tests compare with the register-resident kernels) */
-#define VFT_DEBUG_NO_MULTI_SWEEP 12     /* 1: vft_sweep_batch sweeps its seeds one launch each instead of four per pass over the targets (tests compare); 2 / 4: that many seeds per pass whatever the shard; 0: the built-in choice */
+#define VFT_DEBUG_NO_MULTI_SWEEP 12     /* 1: vft_sweep_batch sweeps its seeds one launch each instead of four per pass over the targets (tests compare); 2 / 4: that many seeds per pass whatever the shard; 8: the per-kind passes stay but a group of leaf seeds and a group of profile seeds no longer share one (k_sweep_nt_mixed_multi off); 0: the built-in choice */
 int vft_debug_option(vft_ctx *ctx, int32_t option, int64_t value);
 
 /* ---- measurement helpers used by bench.py (HIP events on the context's stream) */

@@ -210,6 +210,7 @@ struct vft_ctx {
     size_t kevUsed = 0;
     int64_t kevSweeps = 0;       // sweeps beyond one per timed launch (a pass of k_sweep_nt_leafq_multi covers several)
     bool noMultiSweep = false;   // VFT_DEBUG_NO_MULTI_SWEEP
+    bool noMixedSweep = false;   // VFT_DEBUG_NO_MULTI_SWEEP value 8: leaf and profile groups keep their own passes
     int multiMax = 0;            // seeds per shared pass: 0 = by the shard's size (vft_sweep_batch), 2 / 4 = fixed (VFT_DEBUG_NO_MULTI_SWEEP values 2 / 4)
     bool timeKernels = false;
 };
@@ -2206,6 +2207,59 @@ static int sweep_group(vft_ctx *c, bool leafSeeds, const int *slotOf, const int6
     return VFT_OK;
 }
 
+// can four leaf seeds and four profile seeds share ONE pass (k_sweep_nt_mixed_multi)?  The shard must hold leaves and internal nodes,
+// and the leaf seeds' min / max partials (numbered differently from a leaf-seed pass: see the kernel) must fit their buffers.
+static bool mixed_sweep_fits(vft_ctx *c) {
+    SweepArgs s{};
+    s.lo = c->shardLo;
+    s.hi = c->shardHi < c->maxnode ? c->shardHi : c->maxnode;
+    const unsigned grid = sweep_nt_grid(c, s, true);
+    if (!s.nLeafWG || grid == (unsigned) s.nLeafWG || s.hi <= s.leafEnd) return false;
+    const int64_t N = ((c->d.maxNodes + VFT_TILE - 1) / VFT_TILE + 4) * VFT_TILE;   // (ensure_slots)
+    return (int64_t) cdiv(s.leafEnd - s.lo, VFT_WG) + (int64_t) (grid - (unsigned) s.nLeafWG) <= (int64_t) cdiv(N, VFT_WG);
+}
+
+// a full group of leaf seeds and a full group of profile seeds of a batch in ONE pass over the targets (k_sweep_nt_mixed_multi): results
+// bit for bit those of the two sweep_group calls it replaces; same preconditions, and mixed_sweep_fits
+template <typename REAL>
+static int sweep_mixed(vft_ctx *c, const int *leafPos, const int *profPos, const int64_t *queries, int64_t nActive, int64_t nDiffAllow, double totdiam, const void *mq) {
+    constexpr int S = 4;
+    MixedArgs<REAL, S, S> a;
+    memset((void *) &a, 0, sizeof(a));
+    a.A = arena<REAL>(c);
+    SweepArgs &s = a.s;
+    s.query = queries[profPos[0]];
+    s.lo = c->shardLo;
+    s.hi = c->shardHi < c->maxnode ? c->shardHi : c->maxnode;
+    s.nActive = nActive;
+    s.nDiffAllow = nDiffAllow;
+    s.totdiam = totdiam;
+    s.queryIsLeaf = 0;
+    const unsigned gridP = sweep_nt_grid(c, s, true);   // the profile seeds' geometry: nLeafWG table spans + the internal workgroups
+    a.nInt = (int32_t) (gridP - (unsigned) s.nLeafWG);
+    a.nLeafHeavy = (int32_t) cdiv(s.leafEnd - s.lo, VFT_WG);
+    for (int q = 0; q < S; q++) {
+        a.M.L.Q[q] = qbuf_slot<REAL>(c, leafPos[q]);
+        a.M.L.O[q] = sweepout<REAL>(c, leafPos[q]);
+        a.M.L.query[q] = queries[leafPos[q]];
+        c->slots[(size_t) leafPos[q]].nPart = a.nLeafHeavy + a.nInt;
+        a.M.P.Q[q] = qbuf_slot<REAL>(c, profPos[q]);
+        a.M.P.O[q] = sweepout<REAL>(c, profPos[q]);
+        a.M.P.query[q] = queries[profPos[q]];
+        c->slots[(size_t) profPos[q]].nPart = (int) gridP;
+    }
+    a.M.L.mq = nullptr;
+    a.M.P.mq = (const REAL *) mq;
+    c->nPart = (int) gridP;
+    kernel_event(c);
+    launch((k_sweep_nt_mixed_multi<REAL, S, S>), dim3((unsigned) (a.nInt + a.nLeafHeavy + s.nLeafWG)), dim3(VFT_WG), 0, c->stream, a);
+    kernel_event(c);
+    kernel_event(c);
+    if (c->timeKernels) c->kevSweeps += 2 * S - 1;   // (one triple of events, 2 S sweeps)
+    LAUNCHCHK(c);
+    return VFT_OK;
+}
+
 static int sweep_args_ok(vft_ctx *c, int64_t query, int64_t nActive, int32_t k) {
     if (!c->leavesUp) return fail(c, VFT_ERR_STATE, "vft_sweep before vft_upload_leaves");
     if (query < 0 || query >= c->maxnode || nActive < 3 || k < 0 || k > c->hitsCap)
@@ -2326,7 +2380,23 @@ extern "C" int vft_sweep_batch(vft_ctx *c, int32_t nSeeds, const int64_t *querie
         LAUNCHCHK(c);
     }
     std::vector<char> done((size_t) nSeeds, 0);
+    // a full group of leaf seeds and a full group of profile seeds share one pass: the internal targets are decoded once for both
+    // (single precision: in double precision the merged column loop does not fit the registers and the groups keep their launches)
+    std::vector<char> groupDone(groups.size(), 0);
+    if (c->cfg.precision == 4 && !c->noMixedSweep && !groups.empty() && mixed_sweep_fits(c)) {
+        size_t gl = 0, gp = 0;
+        for (;;) {
+            while (gl < groups.size() && !(groups[gl].leaf && groups[gl].n == 4)) gl++;
+            while (gp < groups.size() && !(!groups[gp].leaf && groups[gp].n == 4)) gp++;
+            if (gl == groups.size() || gp == groups.size()) break;
+            const void *mq = (const void *) ((char *) c->mqBuf + gp * c->mqGroupBytes);
+            if (int r = sweep_mixed<float>(c, groups[gl].pos, groups[gp].pos, queries, nActive, nDiffAllow, totdiam, mq)) return r;
+            for (int q = 0; q < 4; q++) done[(size_t) groups[gl].pos[q]] = done[(size_t) groups[gp].pos[q]] = 1;
+            groupDone[gl++] = groupDone[gp++] = 1;
+        }
+    }
     for (size_t g = 0; g < groups.size(); g++) {
+        if (groupDone[g]) continue;
         const SeedGroup &G = groups[g];
         const void *mq = G.leaf ? nullptr : (const void *) ((char *) c->mqBuf + g * c->mqGroupBytes);
         int r;
@@ -4401,6 +4471,7 @@ extern "C" int vft_debug_option(vft_ctx *c, int32_t option, int64_t value) {
         case VFT_DEBUG_NO_MULTI_SWEEP:
             c->noMultiSweep = value == 1;
             c->multiMax = value == 2 || value == 4 ? (int) value : 0;
+            c->noMixedSweep = value == 8;
             break;
         case VFT_DEBUG_POISON_SELECTION:   // the candidate buffers of every slot filled with 0x7f bytes: what recycled memory looks like
             for (vft_ctx::SweepSlotHost &h: c->slots) {

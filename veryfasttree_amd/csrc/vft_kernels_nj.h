@@ -193,10 +193,13 @@ __device__ __forceinline__ void vft_seq_counts(const uint4 a, const uint4 b, int
 #define VFT_SUB 8   // columns loaded and consumed together (a divisor of VFT_CHUNK)
 #endif
 // code of query column p0 + b (p0 a multiple of 4, b a constant): scalar dword load + scalar bit-field extract
+__device__ __forceinline__ uint32_t vft_query_code(const uint8_t *code, int64_t p0, int b) {
+    const uint32_t w = vft_uniform_load<uint32_t>((const uint32_t *) (code + p0 + (b & ~3)));
+    return (w >> ((b & 3) * 8)) & 0xFFu;
+}
 template <typename REAL>
 __device__ __forceinline__ uint32_t vft_query_code(const QueryBuf<REAL> &Q, int64_t p0, int b) {
-    const uint32_t w = vft_uniform_load<uint32_t>((const uint32_t *) (Q.code + p0 + (b & ~3)));
-    return (w >> ((b & 3) * 8)) & 0xFFu;
+    return vft_query_code(Q.code, p0, b);
 }
 
 // QLEAF (the query is a leaf, code cq per column): piece = 1 - f2[cq] (NJ.tcc:924) and f2 of a plain target code is
@@ -707,15 +710,16 @@ __device__ __forceinline__ double vft_usel(double a, double b, unsigned long lon
                             (int) vft_usel_b32((uint32_t) __double2loint(a), (uint32_t) __double2loint(b), mask));
 }
 
-// S queries on one group of SUB columns
-template <typename REAL, int S, int SUB>
-__device__ __forceinline__ void vft_int_chunk_consume_all(const IntChunkAll<REAL, SUB> &ca, int64_t p0, const MultiLeafQ<REAL, S> &M, double *top, double *denom) {
+// S queries on one group of SUB columns; code[q] = query q's reference codes (QueryBuf::code) - all of a query the column loop needs
+template <typename REAL, int S, int SUB, bool FENCE = false>
+__device__ __forceinline__ void vft_int_chunk_consume_all(const IntChunkAll<REAL, SUB> &ca, int64_t p0, const uint8_t *const *code, double *top, double *denom) {
 #pragma unroll
     for (int b = 0; b < SUB; b++) {
+        if (FENCE) __builtin_amdgcn_sched_barrier(0);   // (a column's temporaries at a time: k_sweep_nt_mixed_multi has no registers to spare)
         const double wd = (double) ca.w[b];
 #pragma unroll
         for (int q = 0; q < S; q++) {
-            const uint32_t cq = vft_query_code<REAL>(M.Q[q], p0, b);   // wave-uniform
+            const uint32_t cq = vft_query_code(code[q], p0, b);   // wave-uniform
             const unsigned long long m0 = (cq & 1u) ? ~0ull : 0ull, m1 = (cq & 2u) ? ~0ull : 0ull;
             const REAL fsel = vft_usel(vft_usel(ca.f[b].x, ca.f[b].y, m0), vft_usel(ca.f[b].z, ca.f[b].w, m0), m1);   // f2[cq & 3]
             // the target's weight, or +0.0 at a gap of the query: a product with a scalar 1.0 / 0.0 (exact: weights are finite and
@@ -785,13 +789,16 @@ __global__ __launch_bounds__(VFT_WG) void k_sweep_nt_leafq_multi(Arena<REAL> A, 
             const int nChunk = A.d.nChunk;
             constexpr int NSUB = VFT_CHUNK / SUB;
             IntChunkAll<REAL, SUB> ca;
+            const uint8_t *code[S];
+#pragma unroll
+            for (int q = 0; q < S; q++) code[q] = M.Q[q].code;
             for (int c = 0; c < nChunk; c++) {
                 uint4 nxt;
 #pragma unroll
                 for (int sub = 0; sub < NSUB; sub++) {
                     vft_int_chunk_load_all<REAL, SUB>(ca, c, sub, cur, wT, mM, mO, fT);
                     if (sub == 0) nxt = cT[(int64_t) (c + 1 < nChunk ? c + 1 : c) * VFT_TILE + lane];
-                    vft_int_chunk_consume_all<REAL, S, SUB>(ca, (int64_t) c * VFT_CHUNK + sub * SUB, M, top, denom);
+                    vft_int_chunk_consume_all<REAL, S, SUB>(ca, (int64_t) c * VFT_CHUNK + sub * SUB, code, top, denom);
                 }
                 cur = nxt;
             }
@@ -821,14 +828,24 @@ __global__ __launch_bounds__(VFT_WG) void k_sweep_nt_leafq_multi(Arena<REAL> A, 
 // while the column before it is being consumed and the scheduler may not move anything across the column boundaries: two columns'
 // scalars live, no spill.  The four products of a column are one vector multiply (v_pk_mul_f32 in single precision: two instructions,
 // each lane's product IEEE as before).
+// The sums are loop-carried and read only by the next group's consume, which sits in another basic block (the loads of
+// vft_int_chunk_load_all are branches): left alone, the compiler sinks a group's whole arithmetic down into a later block - next to
+// the following groups', all their operands live at once, spilled.  An empty asm that "uses" the sums keeps the arithmetic in the
+// block it was written in.
+template <int S>
+__device__ __forceinline__ void vft_pin_sums(double *top, double *denom) {
+#pragma unroll
+    for (int q = 0; q < S; q++) asm volatile("" : "+v"(top[q]), "+v"(denom[q]));
+}
+
 template <typename REAL, int S>
 struct QueryCol {
     REAL w[S];
     typename UVec4<REAL>::type f[S];
 };
 template <typename REAL, int S>
-__device__ __forceinline__ void vft_query_col_load(QueryCol<REAL, S> &c, const MultiLeafQ<REAL, S> &M, int64_t p) {
-    const REAL *src = M.mq + p * VFT_MQ_STRIDE(S);
+__device__ __forceinline__ void vft_query_col_load(QueryCol<REAL, S> &c, const REAL *mq, int64_t p) {
+    const REAL *src = mq + p * VFT_MQ_STRIDE(S);
     const typename UVec4<REAL>::type wv = vft_uniform_load4<REAL>(src + 4 * S);
 #pragma unroll
     for (int q = 0; q < S; q++) {
@@ -838,12 +855,12 @@ __device__ __forceinline__ void vft_query_col_load(QueryCol<REAL, S> &c, const M
 }
 
 template <typename REAL, int S, int SUB>
-__device__ __forceinline__ void vft_int_chunk_consume_prof(const IntChunkAll<REAL, SUB> &ca, int64_t p0, const MultiLeafQ<REAL, S> &M, double *top, double *denom) {
+__device__ __forceinline__ void vft_int_chunk_consume_prof(const IntChunkAll<REAL, SUB> &ca, int64_t p0, const REAL *mq, double *top, double *denom) {
     QueryCol<REAL, S> cur, nxt;
-    vft_query_col_load<REAL, S>(cur, M, p0);
+    vft_query_col_load<REAL, S>(cur, mq, p0);
 #pragma unroll
     for (int b = 0; b < SUB; b++) {
-        if (b + 1 < SUB) vft_query_col_load<REAL, S>(nxt, M, p0 + b + 1);
+        if (b + 1 < SUB) vft_query_col_load<REAL, S>(nxt, mq, p0 + b + 1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int q = 0; q < S; q++) {
@@ -1004,12 +1021,76 @@ __device__ __forceinline__ void vft_leaf_table_wg_multi(const Arena<REAL> &A, co
     }
 }
 
+#define VFT_KARG __attribute__((address_space(4)))
+// the kernel-argument segment at byte `off`, as a pointer whose origin the optimiser does not know: loads through it stay where they
+// are written (after the asm), and are scalar loads
+template <typename T>
+__device__ __forceinline__ const VFT_KARG T *vft_kernarg(size_t off) {
+    const VFT_KARG char *p = (const VFT_KARG char *) __builtin_amdgcn_kernarg_segment_ptr() + off;
+    asm volatile("" : "+s"(p));
+    return (const VFT_KARG T *) p;
+}
+template <typename REAL>
+__device__ __forceinline__ SweepOut<REAL> vft_karg_out(const VFT_KARG SweepOut<REAL> *p) {
+    typedef __attribute__((address_space(1))) REAL *gp_t;   // (buffers in device memory: global, not flat, stores)
+    SweepOut<REAL> o;
+    o.dist = (REAL *) (gp_t) p->dist;
+    o.weight = (REAL *) (gp_t) p->weight;
+    o.crit = (REAL *) (gp_t) p->crit;
+    o.partMin = (REAL *) (gp_t) p->partMin;
+    o.partMax = (REAL *) (gp_t) p->partMax;
+    return o;
+}
+template <typename REAL, int S>
+__device__ __forceinline__ void vft_karg_sentinels(const VFT_KARG MultiLeafQ<REAL, S> *M, int64_t j) {
+#pragma unroll
+    for (int q = 0; q < S; q++) {   // the reference's "illegal join" sentinel (NJ.tcc:3586-3590), as vft_sweep_wants
+        const SweepOut<REAL> O = vft_karg_out<REAL>(&M->O[q]);
+        O.dist[j] = (REAL) 1e20;
+        O.crit[j] = (REAL) 1e20;
+        O.weight[j] = 0;
+    }
+}
+// rows [row0, row0 + S) of the workgroup's reduction arrays: the (min, max) of S seeds' criteria into partial `part` of each
+template <typename REAL, int S>
+__device__ __forceinline__ void vft_block_minmax_karg(REAL *cmin, REAL *cmax, const VFT_KARG MultiLeafQ<REAL, S> *M, int part,
+                                                      REAL (*smin)[VFT_WG / 64], REAL (*smax)[VFT_WG / 64]) {
+    constexpr int NW = VFT_WG / 64;
+#pragma unroll
+    for (int q = 0; q < S; q++) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const REAL a = __shfl_xor(cmin[q], off, 64), b = __shfl_xor(cmax[q], off, 64);
+            cmin[q] = a < cmin[q] ? a : cmin[q];
+            cmax[q] = b > cmax[q] ? b : cmax[q];
+        }
+        if ((threadIdx.x & 63) == 0) {
+            smin[q][threadIdx.x >> 6] = cmin[q];
+            smax[q][threadIdx.x >> 6] = cmax[q];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < S) {
+        const int q = threadIdx.x;
+        REAL lo = smin[q][0], hi = smax[q][0];
+#pragma unroll
+        for (int w = 1; w < NW; w++) {
+            lo = smin[q][w] < lo ? smin[q][w] : lo;
+            hi = smax[q][w] > hi ? smax[q][w] : hi;
+        }
+        const SweepOut<REAL> O = vft_karg_out<REAL>(&M->O[q]);
+        O.partMin[part] = lo;
+        O.partMax[part] = hi;
+    }
+}
+
 // (three wavefronts per SIMD in single precision: at four - 128 VGPRs - 23 registers of the column loop went to scratch, nine scratch
 // accesses per 16-column chunk and 120 MB of extra write traffic per launch (rocprofv3 WRITE_SIZE 181 MB against 60 MB of results);
 // with 137 registers nothing spills: 240 -> 215 us per launch of four profile seeds)
 template <typename REAL, int S>
 __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_profq_multi(Arena<REAL> A, MultiLeafQ<REAL, S> M, SweepArgs s) {
     constexpr int SUB = 8;
+    __shared__ REAL smin[S][VFT_WG / 64], smax[S][VFT_WG / 64];
     const int nT = s.nLeafWG, nHeavy = (int) gridDim.x - nT, blk = (int) blockIdx.x;
     REAL cmin[S], cmax[S];
 #pragma unroll
@@ -1027,22 +1108,21 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
     const int64_t j = s.heavyLo + (int64_t) wg * VFT_WG + threadIdx.x;
     const int lane = (int) (j & 63);
     const int64_t tile = j >> 6;
+    // The seeds' buffers and ids are read where they are used, through vft_kernarg: before the column loop for the sentinels, after it
+    // for the epilogue - the loop itself holds `mq` and nothing else of M (see k_sweep_nt_mixed_multi).  M is the second argument:
+    constexpr size_t offM = (sizeof(Arena<REAL>) + alignof(MultiLeafQ<REAL, S>) - 1) / alignof(MultiLeafQ<REAL, S>) * alignof(MultiLeafQ<REAL, S>);
+    const VFT_KARG MultiLeafQ<REAL, S> *M0 = vft_kernarg<MultiLeafQ<REAL, S>>(offM);
     bool work = false;
     if (j < s.hi && !(nT && j < s.leafEnd)) {
         work = A.parent[j] < 0;
-        if (!work) {   // the reference's "illegal join" sentinel (NJ.tcc:3586-3590), as vft_sweep_wants
-#pragma unroll
-            for (int q = 0; q < S; q++) {
-                M.O[q].dist[j] = (REAL) 1e20;
-                M.O[q].crit[j] = (REAL) 1e20;
-                M.O[q].weight[j] = 0;
-            }
-        }
+        if (!work) vft_karg_sentinels<REAL, S>(M0, j);
     }
-    if (work) {   // (an internal node: the leaves of a profile query belong to the table workgroups - or, without any, do not exist in [heavyLo, hi))
-        double top[S], denom[S];
+    double top[S], denom[S];
 #pragma unroll
-        for (int q = 0; q < S; q++) top[q] = denom[q] = 0;
+    for (int q = 0; q < S; q++) top[q] = denom[q] = 0;
+    const VFT_KARG MultiLeafQ<REAL, S> *M1 = vft_kernarg<MultiLeafQ<REAL, S>>(offM);
+    if (work) {   // (an internal node: the leaves of a profile query belong to the table workgroups - or, without any, do not exist in [heavyLo, hi))
+        const REAL *mq = M1->mq;
         const int64_t pt = (int64_t) __builtin_amdgcn_readfirstlane((int) (tile - A.d.firstProfTile));
         const uint4 *cT = A.profC + vft_c_idx(A.d, pt, 0, 0);
         const vft_smask_t mM = (vft_smask_t) (A.colMask + vft_meta_idx(A.d, pt, 0));
@@ -1058,20 +1138,205 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
             for (int sub = 0; sub < VFT_CHUNK / SUB; sub++) {
                 vft_int_chunk_load_all<REAL, SUB>(ca, c, sub, cur, wT, mM, mO, fT);
                 if (sub == 0) nxt = cT[(int64_t) (c + 1 < nChunk ? c + 1 : c) * VFT_TILE + lane];
-                vft_int_chunk_consume_prof<REAL, S, SUB>(ca, (int64_t) c * VFT_CHUNK + sub * SUB, M, top, denom);
+                vft_int_chunk_consume_prof<REAL, S, SUB>(ca, (int64_t) c * VFT_CHUNK + sub * SUB, mq, top, denom);
+                vft_pin_sums<S>(top, denom);
             }
             cur = nxt;
         }
+    }
+    const VFT_KARG MultiLeafQ<REAL, S> *Mk = vft_kernarg<MultiLeafQ<REAL, S>>(offM);   // after the loop: the epilogue's
+    if (work) {
 #pragma unroll
         for (int q = 0; q < S; q++) {
             const REAL weight = (REAL) (denom[q] > 0 ? denom[q] : 0.01);
             const REAL dist = (REAL) (denom[q] > 0 ? top[q] / denom[q] : 1.0);
             SweepArgs sq = s;
-            sq.query = M.query[q];
-            vft_sweep_finish<REAL, MODE_CRIT>(A, sq, M.O[q], j, dist, weight, false, cmin[q], cmax[q]);
+            sq.query = Mk->query[q];
+            vft_sweep_finish<REAL, MODE_CRIT>(A, sq, vft_karg_out<REAL>(&Mk->O[q]), j, dist, weight, false, cmin[q], cmax[q]);
         }
     }
-    vft_block_minmax_multi<REAL, S>(cmin, cmax, M.O, nT + wg);
+    vft_block_minmax_karg<REAL, S>(cmin, cmax, vft_kernarg<MultiLeafQ<REAL, S>>(offM), nT + wg, smin, smax);
+}
+
+// ---- SL leaf seeds AND SP profile seeds in one launch (vft_sweep_batch pairs a full group of each): the internal targets are streamed
+// and decoded ONCE - masks and offsets, slots, code byte, weight, vector (vft_int_chunk_load_all) - and both kinds of seed are evaluated
+// on the decoded columns, the profile seeds first (vft_int_chunk_consume_prof), then the leaf seeds (vft_int_chunk_consume_all); per
+// (seed, target) the operations are those of the per-kind kernels, in their order: same bits.  Workgroups, in launch order:
+//   1. nInt "internal" ones over [s.heavyLo, s.hi), highest ids first, ids >= s.leafEnd only: all SL + SP seeds
+//   2. nLeafHeavy over [s.lo, s.leafEnd), a leaf per lane: the leaf seeds' popcount distances (k_sweep_nt_leafq_multi's leaf targets)
+//   3. s.nLeafWG table workgroups over the same leaves: the profile seeds (vft_leaf_table_wg_multi)
+// Every (seed, target) buffer entry belongs to exactly one workgroup.  Min / max partials: a profile seed's are numbered as in
+// k_sweep_nt_profq_multi (span, nLeafWG + wg: nLeafWG + nInt of them), a leaf seed's [leaf-range workgroup, nLeafHeavy + wg]
+// (nLeafHeavy + nInt) - each seed's range is written completely, by workgroups that serve it.
+//
+// The seeds' buffers and ids (2 x MultiLeafQ) are needed before the column loop (sentinels) and after it (epilogue), the loop itself
+// wants one pointer for the profile seeds (mq) and SL for the leaf seeds (codes).  Passed as a plain kernel argument the compiler loads
+// all of it at the top and keeps it in SGPRs across the loop - more than there are, so they travel through v_writelane / v_readlane
+// inside the loop.  Here the argument block is read through a pointer the compiler cannot see through (vft_kernarg), at the place of
+// use: what the epilogue needs is loaded after the loop.
+template <typename REAL, int SL, int SP>
+struct MixedQ {
+    MultiLeafQ<REAL, SL> L;
+    MultiLeafQ<REAL, SP> P;
+};
+template <typename REAL, int SL, int SP>
+struct MixedArgs {   // the kernel's only argument: the offset of M in the kernel-argument segment is offsetof(MixedArgs, M)
+    Arena<REAL> A;
+    SweepArgs s;     // the PROFILE seeds' geometry (sweep_nt_grid with the table path): lo, hi, leafEnd, heavyLo, nLeafWG
+    int32_t nInt, nLeafHeavy;
+    MixedQ<REAL, SL, SP> M;
+};
+template <typename REAL, int SL, int SP>
+__global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_mixed_multi(MixedArgs<REAL, SL, SP> a) {
+    typedef MixedArgs<REAL, SL, SP> Args;
+    constexpr int SUB = 8, NW = VFT_WG / 64;
+    constexpr size_t offL = offsetof(Args, M) + offsetof(decltype(Args::M), L), offP = offsetof(Args, M) + offsetof(decltype(Args::M), P);
+    __shared__ REAL smin[SL + SP][NW], smax[SL + SP][NW];
+    const Arena<REAL> &A = a.A;
+    const SweepArgs &s = a.s;
+    const int blk = (int) blockIdx.x, nInt = a.nInt, nLH = a.nLeafHeavy, nT = s.nLeafWG;
+    REAL cminP[SP], cmaxP[SP], cminL[SL], cmaxL[SL];
+#pragma unroll
+    for (int q = 0; q < SP; q++) {
+        cminP[q] = (REAL) 1e30;
+        cmaxP[q] = (REAL) -1e30;
+    }
+#pragma unroll
+    for (int q = 0; q < SL; q++) {
+        cminL[q] = (REAL) 1e30;
+        cmaxL[q] = (REAL) -1e30;
+    }
+    if (blk >= nInt + nLH) {   // 3. a table workgroup: span `span` of the leaves against the profile seeds
+        const int span = blk - nInt - nLH;
+        const VFT_KARG MultiLeafQ<REAL, SP> *Pk = vft_kernarg<MultiLeafQ<REAL, SP>>(offP);
+        MultiLeafQ<REAL, SP> M;
+#pragma unroll
+        for (int q = 0; q < SP; q++) {
+            M.Q[q].w = Pk->Q[q].w;
+            M.Q[q].code = Pk->Q[q].code;
+            M.Q[q].f = Pk->Q[q].f;
+            M.Q[q].enc = Pk->Q[q].enc;
+            M.Q[q].tab = Pk->Q[q].tab;
+            M.O[q] = vft_karg_out<REAL>(&Pk->O[q]);
+            M.query[q] = Pk->query[q];
+        }
+        M.mq = Pk->mq;
+        vft_leaf_table_wg_multi<REAL, SP>(A, M, s, s.lo + (int64_t) span * VFT_LEAF_SPAN, cminP, cmaxP);
+        vft_block_minmax_karg<REAL, SP>(cminP, cmaxP, vft_kernarg<MultiLeafQ<REAL, SP>>(offP), span, smin, smax);
+        return;
+    }
+    if (blk >= nInt) {   // 2. leaves against the leaf seeds: encoded bytes, integer counts (seqDist, NJ.tcc:1601-1612)
+        const int wg = nLH - 1 - (blk - nInt);
+        const int64_t j = s.lo + (int64_t) wg * VFT_WG + threadIdx.x;
+        // (vft_kernarg's asm wants uniform control flow: the pointers are made outside the per-lane branches)
+        const VFT_KARG MultiLeafQ<REAL, SL> *Lk = vft_kernarg<MultiLeafQ<REAL, SL>>(offL);
+        bool work = false;
+        if (j < s.leafEnd) {
+            work = A.parent[j] < 0;
+            if (!work) vft_karg_sentinels<REAL, SL>(Lk, j);
+        }
+        if (work) {
+            const uint4 *enc[SL];
+            int nUse[SL], nSame[SL];
+#pragma unroll
+            for (int q = 0; q < SL; q++) {
+                enc[q] = Lk->Q[q].enc;
+                nUse[q] = nSame[q] = 0;
+            }
+            const int lane = (int) (j & 63);
+            const int64_t tile = j >> 6;
+            for (int c = 0; c < A.d.nChunk; c++) {
+                const uint4 t = A.leafT[vft_leaf_idx(A.d, tile, c, lane)];
+#pragma unroll
+                for (int q = 0; q < SL; q++) vft_seq_counts(t, enc[q][c], nUse[q], nSame[q]);
+            }
+#pragma unroll
+            for (int q = 0; q < SL; q++) {
+                const double top = (double) (nUse[q] - nSame[q]);
+                const REAL weight = (REAL) (double) nUse[q];
+                const REAL dist = (REAL) (nUse[q] > 0 ? top / (double) nUse[q] : 1.0);
+                SweepArgs sq = s;
+                sq.query = Lk->query[q];
+                vft_sweep_finish<REAL, MODE_CRIT>(A, sq, vft_karg_out<REAL>(&Lk->O[q]), j, dist, weight, true, cminL[q], cmaxL[q]);
+            }
+        }
+        vft_block_minmax_karg<REAL, SL>(cminL, cmaxL, vft_kernarg<MultiLeafQ<REAL, SL>>(offL), wg, smin, smax);
+        return;
+    }
+    // 1. internal targets against all seeds
+    const int wg = nInt - 1 - blk;   // highest ids first, as in k_sweep_nt
+    const int64_t j = s.heavyLo + (int64_t) wg * VFT_WG + threadIdx.x;
+    const int lane = (int) (j & 63);
+    const int64_t tile = j >> 6;
+    // (vft_kernarg's asm wants uniform control flow: the pointers are made outside the per-lane branches)
+    const VFT_KARG MixedQ<REAL, SL, SP> *M0 = vft_kernarg<MixedQ<REAL, SL, SP>>(offsetof(Args, M));
+    bool work = false;
+    if (j < s.hi && j >= s.leafEnd) {
+        work = A.parent[j] < 0;
+        if (!work) {
+            vft_karg_sentinels<REAL, SP>(&M0->P, j);
+            vft_karg_sentinels<REAL, SL>(&M0->L, j);
+        }
+    }
+    double topP[SP], denomP[SP], topL[SL], denomL[SL];
+#pragma unroll
+    for (int q = 0; q < SP; q++) topP[q] = denomP[q] = 0;
+#pragma unroll
+    for (int q = 0; q < SL; q++) topL[q] = denomL[q] = 0;
+    const VFT_KARG MixedQ<REAL, SL, SP> *M1 = vft_kernarg<MixedQ<REAL, SL, SP>>(offsetof(Args, M));
+    if (work) {
+        // all the column loop needs of the seeds
+        const REAL *mq = M1->P.mq;
+        const uint8_t *code[SL];
+#pragma unroll
+        for (int q = 0; q < SL; q++) code[q] = M1->L.Q[q].code;
+        const int64_t pt = (int64_t) __builtin_amdgcn_readfirstlane((int) (tile - A.d.firstProfTile));
+        const uint4 *cT = A.profC + vft_c_idx(A.d, pt, 0, 0);
+        const vft_smask_t mM = (vft_smask_t) (A.colMask + vft_meta_idx(A.d, pt, 0));
+        const vft_soff_t mO = (vft_soff_t) (A.colOff + vft_meta_idx(A.d, pt, 0));
+        const REAL *wT = A.profW + vft_wstream_base(A.d, pt);
+        const REAL *fT = A.profF + vft_fstream_base(A.d, pt);
+        uint4 cur = cT[lane];
+        const int nChunk = A.d.nChunk;
+        IntChunkAll<REAL, SUB> ca;
+        for (int c = 0; c < nChunk; c++) {
+            uint4 nxt;
+#pragma unroll
+            for (int sub = 0; sub < VFT_CHUNK / SUB; sub++) {
+                const int64_t p0 = (int64_t) c * VFT_CHUNK + sub * SUB;
+                vft_int_chunk_load_all<REAL, SUB>(ca, c, sub, cur, wT, mM, mO, fT);
+                if (sub == 0) nxt = cT[(int64_t) (c + 1 < nChunk ? c + 1 : c) * VFT_TILE + lane];
+                vft_int_chunk_consume_prof<REAL, SP, SUB>(ca, p0, mq, topP, denomP);
+                vft_pin_sums<SP>(topP, denomP);
+                __builtin_amdgcn_sched_barrier(0);   // one kind's query scalars live at a time: mq columns, then code bytes
+                vft_int_chunk_consume_all<REAL, SL, SUB, true>(ca, p0, code, topL, denomL);
+                vft_pin_sums<SL>(topL, denomL);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            cur = nxt;
+        }
+    }
+    const VFT_KARG MixedQ<REAL, SL, SP> *Mk = vft_kernarg<MixedQ<REAL, SL, SP>>(offsetof(Args, M));   // after the loop: the epilogue's
+    if (work) {
+#pragma unroll
+        for (int q = 0; q < SP; q++) {
+            const REAL weight = (REAL) (denomP[q] > 0 ? denomP[q] : 0.01);
+            const REAL dist = (REAL) (denomP[q] > 0 ? topP[q] / denomP[q] : 1.0);
+            SweepArgs sq = s;
+            sq.query = Mk->P.query[q];
+            vft_sweep_finish<REAL, MODE_CRIT>(A, sq, vft_karg_out<REAL>(&Mk->P.O[q]), j, dist, weight, false, cminP[q], cmaxP[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < SL; q++) {
+            const REAL weight = (REAL) (denomL[q] > 0 ? denomL[q] : 0.01);
+            const REAL dist = (REAL) (denomL[q] > 0 ? topL[q] / denomL[q] : 1.0);
+            SweepArgs sq = s;
+            sq.query = Mk->L.query[q];
+            vft_sweep_finish<REAL, MODE_CRIT>(A, sq, vft_karg_out<REAL>(&Mk->L.O[q]), j, dist, weight, false, cminL[q], cmaxL[q]);
+        }
+    }
+    vft_block_minmax_karg<REAL, SP>(cminP, cmaxP, vft_kernarg<MultiLeafQ<REAL, SP>>(offP), nT + wg, smin, smax);
+    vft_block_minmax_karg<REAL, SL>(cminL, cmaxL, vft_kernarg<MultiLeafQ<REAL, SL>>(offL), nLH + wg, smin + SP, smax + SP);
 }
 
 // ------------------------------------------------------------------------------------------------ generic pair
