@@ -75,6 +75,16 @@ int vft_synchronize(vft_ctx *ctx);
 int vft_device_malloc(vft_ctx *ctx, int64_t bytes, void **d_ptr);
 int vft_device_free(vft_ctx *ctx, void *d_ptr);
 int vft_device_upload(vft_ctx *ctx, void *d_dst, const void *src, int64_t bytes);
+/* Page-locked host buffers and stream-ordered copies into them, for callers that stream a result larger than they want to
+   hold (host/SeqMatrix.h): vft_download_async queues the copy of `bytes` bytes from device memory behind the work already on
+   the context's stream and returns; vft_download_wait(slot) returns once the copy last started in that slot has landed
+   (work queued behind it keeps running).  dst should come from vft_host_malloc (a pageable destination makes the copy
+   synchronous).  slot: 0 .. VFT_DOWNLOAD_SLOTS - 1. */
+#define VFT_DOWNLOAD_SLOTS 4
+int vft_host_malloc(vft_ctx *ctx, int64_t bytes, void **ptr);
+int vft_host_free(vft_ctx *ctx, void *ptr);
+int vft_download_async(vft_ctx *ctx, void *dst, const void *d_src, int64_t bytes, int32_t slot);
+int vft_download_wait(vft_ctx *ctx, int32_t slot);
 
 /* ---- inputs */
 /* Leaf profiles from codes[n_seqs][n_pos] (what seqsToProfiles builds, NJ.tcc:382-457). */
@@ -362,6 +372,20 @@ int vft_exhaustive_search(vft_ctx *ctx, int64_t n_active, vft_exhaustive_best_t 
    order, dist[n_live] = the stored distance of (node, nodes[k]) (numeric_t, host; the entry of the node itself is
    unspecified).  nodes / dist may be NULL.  Waits. */
 int vft_exhaustive_row(vft_ctx *ctx, int64_t node, int64_t *n_live, int64_t *nodes, void *dist);
+
+/* ---- `-makematrix` (printDistances, NJ.tcc:274-288; VeryFastTreeImpl.tcc:67-73): rows [r0, r1) of the n_seqs x n_seqs matrix
+   of sequence distances, every uploaded leaf against every uploaded leaf, diagonal included.  Entry (i, j), codes1 = i: seqDist
+   on the leaf codes (NJ.tcc:1601-1624: %-different counts for nucleotides, the `distances` table of vft_set_distance_matrix
+   summed in column order into a double for proteins), narrowed to numeric_t; with log_correct != 0 logCorrect (NJ.tcc:322-330:
+   Jukes-Cantor for nucleotides, scoredist-like with the matrix, libm's log restated in csrc/vft_glibc_log.h) narrowed again;
+   then `dist <= 0 ? 0 : dist` (NJ.tcc:284) - the number whose " %f" the reference prints.  log_correct = 0 is `-rawdist`.
+   d_out: device memory, numeric_t[(r1 - r0) * ld] with ld >= n_seqs, entry (i, j) at (i - r0) * ld + j; the columns from
+   n_seqs to ld of a row are not written.  Stream-ordered; with out != NULL (host, same size and stride) the rows are copied
+   there as well and the call waits.  The leaves must be uploaded (every sequence of the alignment, not the unique ones: the
+   mode does not uniquify); 0 <= r0 < r1 <= n_seqs; a context created with max_nodes == n_seqs is enough.  The kernel follows the
+   alphabet: nucleotides WITH a distance matrix and proteins WITHOUT one are VFT_ERR_INVALID (the reference's command line
+   offers neither, VeryFastTree.cpp:96-98).  Nothing of the profile arena is read or written. */
+int vft_seq_matrix_rows(vft_ctx *ctx, int64_t r0, int64_t r1, int32_t log_correct, void *d_out, int64_t ld, void *out);
 
 /* ---- likelihood (ML phase)
  * pairLogLk (NJ.tcc:1192-1447) for n independent pairs; site_lk (n x n_pos doubles, host) may be NULL, when

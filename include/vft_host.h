@@ -196,6 +196,19 @@ int vft_nj_out_profile_block(int32_t parts, int32_t world, int32_t block, int64_
    alpha, the factor every branch length was multiplied by (the reference's "Gamma(20) LogLk = .. alpha = .. rescaling lengths by ..") */
 int vft_nj_last_gamma(double *out);
 
+/* `-makematrix` (VeryFastTreeImpl.tcc:67-73 -> printDistances, NJ.tcc:274-288): writes to the file descriptor fd what the reference
+   prints - per sequence its name, " %f" of the distance to every sequence in input order (the diagonal included), a newline; no
+   header.  ctx: a context of `precision` with the n_seqs sequences of the WHOLE alignment uploaded (vft_upload_leaves; the mode does not
+   uniquify: duplicate sequences give duplicate rows) and, for proteins, the distance matrix set; max_nodes == n_seqs is enough.
+   names: n_seqs NUL-terminated names back to back; a repeated name is an error, as in the reference.  log_correct = 0 is `-rawdist`.
+   The matrix is computed by vft_seq_matrix_rows in slabs of slab_rows rows (<= 0: as many as make two device and two page-locked host
+   slabs fill 256 MiB, at least one), two in flight - memory does not depend on n_seqs^2 - and the rows of a slab are formatted by up to 16
+   threads (snprintf "%f" in the C locale).  comm: NULL or one rank; more ranks are refused (host/SeqMatrix.h).
+   seconds[4] (may be NULL): waiting for the device, formatting, write(2), the whole call; counts[3] (may be NULL): slabs, rows per slab,
+   bytes written. */
+int vft_nj_make_matrix(vft_ctx *ctx, int64_t n_seqs, int32_t precision, const char *names, int32_t log_correct, int64_t slab_rows,
+                       int32_t fd, const vft_comm *comm, double *seconds, int64_t *counts, char *err, int32_t err_len);
+
 /* The first n values of the random stream the bootstrap columns are drawn from (Knuth's ran_array at its default
    seed, as the reference uses it, Knuth.cpp:95-111): exported so that tests can pin the host generator. */
 void vft_knuth_stream(double *out, int64_t n);

@@ -7,6 +7,7 @@ or - with -mllen - the tree of `VeryFastTree -nt -nome -mllen [-nocat | -cat N] 
     python tools/nj_tree.py in.fasta -full [-gtr] [-double] [-nosupport] > tree.nwk     # what plain `VeryFastTree -nt [-gtr]` prints
     python tools/nj_tree.py in.fasta -full -lg -double > tree.nwk     # proteins: `VeryFastTree -lg -double-precision` (-aa / -jtt, -wag, -lg)
     python tools/nj_tree.py in.fasta -full -threads 64 [-gamma] [-spr N] > tree.nwk   # the schedule of `VeryFastTree -threads 64`; -gamma; -spr N rounds
+    python tools/nj_tree.py -makematrix [-rawdist] [-aa] [-double] in.fasta > matrix.txt   # `VeryFastTree [-nt] [-rawdist] [-double-precision] -makematrix`
 
 Neighbour joining with top hits on the device (veryfasttree_amd/host/NJDriver.h), the root, minimum-evolution branch
 lengths (updateBranchLengths), local-bootstrap supports (1000 resamples, reliabilityNJ) and printNJ; -nj-lengths keeps
@@ -16,6 +17,10 @@ lengths on that topology (optimizeAllBranchLengths rounds, CAT rate categories u
 -slow: the exhaustive search of the reference's `-slow` (every join is the best pair of all active nodes, on a distance
 matrix kept on the device) instead of top hits; not together with -fastest (as in the reference) or -full (the NNI and
 SPR stages of a -slow run are not built).
+-makematrix: no tree - the log-corrected distance of every pair of input sequences, computed on the device and printed the
+way `VeryFastTree [-nt] [-rawdist] [-double-precision] -makematrix in.fasta` prints it (one row per sequence: its name, then
+" %f" per sequence; proteins with -aa: BLOSUM45 distances).  Every sequence is kept (no uniquify); repeated names are an
+error; not together with any tree option.
 Sequence normalisation and uniquify follow Alignment.cpp:453-526 (U -> T, '.' -> '-', duplicates by sequence string in
 first-occurrence order; N -> X for nucleotides)."""
 import os, sys
@@ -23,7 +28,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from veryfasttree_amd import HipProfileOps
-from veryfasttree_amd.backend import nj_newick
+from veryfasttree_amd.backend import make_matrix, nj_newick, VftError
 from veryfasttree_amd.synth import ALPHABET_AA, ALPHABET_NT, NOCODE
 
 
@@ -44,8 +49,44 @@ def read_fasta(path):
     return names, seqs
 
 
+def codes_of(seqs, aa):
+    """Alignment.cpp:453-471: '.' -> '-' always; for nucleotides U -> T and N -> X; anything outside the alphabet is NOCODE"""
+    seqs = [s.upper().replace(".", "-") for s in seqs]
+    if not aa:
+        seqs = [s.replace("U", "T").replace("N", "X") for s in seqs]
+    lut = np.full(256, NOCODE, np.uint8)
+    for i, ch in enumerate(ALPHABET_AA if aa else ALPHABET_NT):
+        lut[ord(ch)] = i
+    return seqs, np.stack([lut[np.frombuffer(s.encode("ascii", "replace"), np.uint8)] for s in seqs])
+
+
+MAKEMATRIX_FLAGS = ("-makematrix", "-rawdist", "-aa", "-double")
+
+
+def main_makematrix(args):
+    """`-makematrix`: every sequence of the alignment, in input order, against every sequence"""
+    other = [a for a in args if a.startswith("-") and a not in MAKEMATRIX_FLAGS]
+    if other:
+        sys.exit("-makematrix prints distances and builds no tree: it cannot be combined with %s (allowed: -rawdist, -aa, -double)" % " ".join(other))
+    paths = [a for a in args if not a.startswith("-")]
+    if len(paths) != 1:
+        sys.exit("-makematrix needs exactly one alignment file")
+    names, seqs = read_fasta(paths[0])
+    if not seqs or len({len(s) for s in seqs}) != 1:
+        sys.exit("sequences have different lengths: not an alignment")
+    aa = "-aa" in args
+    _, codes_all = codes_of(seqs, aa)
+    sys.stdout.flush()
+    try:   # the text goes to standard output, as the reference's does even with -out
+        make_matrix(codes_all, names, 20 if aa else 4, np.float64 if "-double" in args else np.float32, "-rawdist" in args, 1)
+    except VftError as e:
+        sys.exit(str(e))
+
+
 def main():
     args = sys.argv[1:]
+    if "-makematrix" in args:
+        return main_makematrix(args)
     if not args or args[0].startswith("-"):
         sys.exit(__doc__)
     fastest, double, nj_len = "-fastest" in args, "-double" in args, "-nj-lengths" in args

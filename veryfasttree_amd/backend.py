@@ -35,6 +35,7 @@ EXPORTS = [
     "vft_join_nodes", "vft_profile_distances", "vft_split_supports", "vft_timer_start", "vft_timer_stop_ms", "vft_sweep_kernel_ms", "vft_sweep_table_kernel_ms", "vft_sweep_kernel_sweeps",
     "vft_debug_log", "vft_debug_option", "vft_tophits_create", "vft_tophits_upload", "vft_tophits_download", "vft_tophits_best", "vft_tophits_join", "vft_tophits_refresh", "vft_nj_engine_create", "vft_nj_engine_set_state", "vft_nj_engine_get_state", "vft_nj_engine_visible_set", "vft_nj_engine_visible_get", "vft_nj_engine_nodes_set", "vft_nj_engine_topvisible_set", "vft_nj_engine_topvisible_get", "vft_nj_engine_reset_candidates", "vft_nj_engine_enqueue", "vft_nj_engine_poll", "vft_nj_engine_resume", "vft_nj_engine_log", "vft_nj_engine_adopt", "vft_leaf_block_distances", "vft_set_shard_mode", "vft_join_fused", "vft_block_distances", "vft_pair_distances_refresh",
     "vft_exhaustive_create", "vft_exhaustive_destroy", "vft_exhaustive_fill", "vft_exhaustive_join", "vft_exhaustive_search", "vft_exhaustive_row",
+    "vft_seq_matrix_rows", "vft_host_malloc", "vft_host_free", "vft_download_async", "vft_download_wait",
 ]
 
 
@@ -51,7 +52,7 @@ HIT_F32 = np.dtype([("j", np.int32), ("dist", np.float32), ("weight", np.float32
 HIT_F64 = np.dtype([("j", np.int64), ("dist", np.float64), ("weight", np.float64), ("criterion", np.float64)])
 
 HOST_LIB_PATH = os.path.join(LIB_DIR, "libvft_host.so")
-HOST_EXPORTS = ["vft_nj_run", "vft_nj_newick", "vft_nj_ml_newick", "vft_nj_last_join_crcs", "vft_nj_last_stage_seconds", "vft_nj_last_walk_dual", "vft_nj_last_lane_exchange", "vft_nj_lane_share", "vft_nj_out_profile_block", "vft_nj_last_gamma", "vft_tree_partitioning", "vft_knuth_stream", "vft_ml_lengths", "vft_gtr_tables",
+HOST_EXPORTS = ["vft_nj_run", "vft_nj_newick", "vft_nj_ml_newick", "vft_nj_last_join_crcs", "vft_nj_last_stage_seconds", "vft_nj_last_walk_dual", "vft_nj_last_lane_exchange", "vft_nj_lane_share", "vft_nj_out_profile_block", "vft_nj_last_gamma", "vft_nj_make_matrix", "vft_tree_partitioning", "vft_knuth_stream", "vft_ml_lengths", "vft_gtr_tables",
                 "vft_aa_model_tables", "vft_blosum45_tables", "vft_aa_model_as_distance_tables"]
 
 
@@ -297,6 +298,39 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
     return out.value.decode()
 
 
+def make_matrix(codes_all, names, n_codes, dtype, rawdist, out_fd, slab_rows=None, comm=None, return_times=False):
+    """`-makematrix` (printDistances, NJ.tcc:274-288) through the host driver (vft_nj_make_matrix): writes to the file descriptor
+    out_fd the reference's text for the alignment codes_all - EVERY row, in input order, duplicates included - and `names`.
+    n_codes 4: %-different distances, Jukes-Cantor correction; 20: the BLOSUM45 distances, scoredist correction; rawdist: no
+    correction.  slab_rows: rows per device slab (None: from the driver's byte budget).  return_times: the driver's split
+    (dict of seconds and counts)."""
+    lib = load_host_library()
+    codes_all = np.ascontiguousarray(codes_all, np.uint8)
+    n, L = codes_all.shape
+    if len(names) != n:
+        raise VftError("-makematrix: %d names for %d sequences" % (len(names), n))
+    dt = np.dtype(dtype)
+    ops = HipProfileOps(n, L, n_codes, dt, max_nodes=n)
+    try:
+        ops.upload_leaves(codes_all)
+        if n_codes == 20:
+            t = distance_tables(None, dt)
+            ops.set_distance_matrix(t["distances"], t["codefreq"], t["eigenval"], t["eigentot"])
+        blob = b"".join(nm.encode() + b"\0" for nm in names)
+        sec, cnt = np.zeros(4, np.float64), np.zeros(3, np.int64)
+        err = C.create_string_buffer(512)
+        rc = lib.vft_nj_make_matrix(ops.ctx, I64(n), I32(dt.itemsize), blob, I32(0 if rawdist else 1), I64(slab_rows or 0), I32(out_fd),
+                                    comm.pointer() if comm is not None else None, _ptr(sec), _ptr(cnt), err, I32(512))
+        if rc != 0:
+            raise VftError(err.value.decode() or "vft_nj_make_matrix failed")
+    finally:
+        ops.close()
+    if return_times:
+        return dict(device_wait=float(sec[0]), format=float(sec[1]), write=float(sec[2]), total=float(sec[3]), slabs=int(cnt[0]),
+                    slab_rows=int(cnt[1]), bytes=int(cnt[2]))
+    return None
+
+
 STAGES = ("nj", "me_nni_spr", "of_which_spr", "me_lengths_supports", "ml_stage", "of_which_ml_nni", "of_which_sh_supports", "of_which_model_fits")
 
 
@@ -489,6 +523,27 @@ class HipProfileOps:
         nodes, dist = np.zeros(n.value, np.int64), np.zeros(n.value, self.dt)
         self._chk(self.lib.vft_exhaustive_row(self.ctx, I64(node), C.byref(n), _ptr(nodes), _ptr(dist)))
         return nodes, dist
+
+    # ---- `-makematrix`: all-pairs sequence distances (vft_seq_matrix_rows)
+    def seq_matrix_rows(self, r0, r1, log_correct=True, ld=None, out=None):
+        """Rows [r0, r1) of the n_seqs x n_seqs matrix the reference's -makematrix prints (printDistances, NJ.tcc:274-288), as
+        numbers of the context's precision: a [r1 - r0, n_seqs] array.  ld / out (tests): the row stride, and a [rows, ld] array to
+        receive the copy - its columns from n_seqs on keep what the caller put there."""
+        rows = max(int(r1) - int(r0), 0)
+        ld = self.n_seqs if ld is None else int(ld)
+        nbytes = max(rows * ld, 1) * self.dt.itemsize
+        d_out = P()
+        self._chk(self.lib.vft_device_malloc(self.ctx, I64(nbytes), C.byref(d_out)))
+        try:
+            if out is None:
+                out = np.zeros((rows, ld), self.dt)
+            else:
+                assert out.dtype == self.dt and out.shape == (rows, ld) and out.flags.c_contiguous
+                self._chk(self.lib.vft_device_upload(self.ctx, d_out, _ptr(out), I64(out.nbytes)))
+            self._chk(self.lib.vft_seq_matrix_rows(self.ctx, I64(r0), I64(r1), I32(1 if log_correct else 0), d_out, I64(ld), _ptr(out)))
+        finally:
+            self.lib.vft_device_free(self.ctx, d_out)
+        return out[:, :self.n_seqs]
 
     def out_distance_mirror(self):
         """numpy views of the host-mapped mirrors of outDistances[] / nOutDistActive[] (vft_out_distance_mirror): what the

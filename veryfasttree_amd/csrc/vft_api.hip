@@ -30,6 +30,7 @@ VFT_ML_LONG_INSTANCES(extern)    // compiled in vft_ml_kernels_long.hip
 #include "vft_kernels_njengine.h"
 #include "vft_kernels_walk.h"
 #include "vft_kernels_exhaustive.h"
+#include "vft_kernels_seqmatrix.h"
 
 VFT_WALK_SERVER_INSTANCES(extern)   // compiled in vft_walk_kernels.hip
 
@@ -206,6 +207,7 @@ struct vft_ctx {
     std::vector<int32_t> exSlotOfH;      // [max_nodes]
     // timing
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t dlEv[VFT_DOWNLOAD_SLOTS] = {};   // vft_download_async: one event per slot, made on first use
     std::vector<hipEvent_t> kev;
     size_t kevUsed = 0;
     int64_t kevSweeps = 0;       // sweeps beyond one per timed launch (a pass of k_sweep_nt_leafq_multi covers several)
@@ -683,6 +685,8 @@ extern "C" int vft_destroy(vft_ctx *c) {
     for (hipEvent_t e : c->kev) hipEventDestroy(e);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
+    for (hipEvent_t e : c->dlEv)
+        if (e) hipEventDestroy(e);
     if (c->ownStream) hipStreamDestroy(c->ownStream);
     delete c;
     return VFT_OK;
@@ -720,6 +724,34 @@ extern "C" int vft_device_upload(vft_ctx *c, void *dst, const void *src, int64_t
     if (!c || !dst || !src || bytes < 0) return VFT_ERR_INVALID;
     HIPCHK(c, hipMemcpyAsync(dst, src, (size_t) bytes, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VFT_OK;
+}
+
+extern "C" int vft_host_malloc(vft_ctx *c, int64_t bytes, void **p) {
+    if (!c || !p || bytes < 0) return VFT_ERR_INVALID;
+    HIPCHK(c, hipHostMalloc(p, bytes ? (size_t) bytes : 1, hipHostMallocDefault));
+    return VFT_OK;
+}
+
+extern "C" int vft_host_free(vft_ctx *c, void *p) {
+    if (!c) return VFT_ERR_INVALID;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipHostFree(p));
+    return VFT_OK;
+}
+
+extern "C" int vft_download_async(vft_ctx *c, void *dst, const void *dSrc, int64_t bytes, int32_t slot) {
+    if (!c || !dst || !dSrc || bytes < 0 || slot < 0 || slot >= VFT_DOWNLOAD_SLOTS) return VFT_ERR_INVALID;
+    if (!c->dlEv[slot]) HIPCHK(c, hipEventCreateWithFlags(&c->dlEv[slot], hipEventDisableTiming));
+    HIPCHK(c, hipMemcpyAsync(dst, dSrc, (size_t) bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->dlEv[slot], c->stream));
+    return VFT_OK;
+}
+
+extern "C" int vft_download_wait(vft_ctx *c, int32_t slot) {
+    if (!c || slot < 0 || slot >= VFT_DOWNLOAD_SLOTS) return VFT_ERR_INVALID;
+    if (!c->dlEv[slot]) return fail(c, VFT_ERR_STATE, "vft_download_wait: nothing was started in slot %d", (int) slot);
+    HIPCHK(c, hipEventSynchronize(c->dlEv[slot]));
     return VFT_OK;
 }
 
@@ -2880,6 +2912,41 @@ extern "C" int vft_leaf_block_distances(vft_ctx *c, int64_t nA, const int64_t *a
     HIPCHK(c, hipMemcpyAsync(weight, o + oB, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(crit, o + 2 * oB, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return VFT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- all-pairs matrix (-makematrix)
+extern "C" int vft_seq_matrix_rows(vft_ctx *c, int64_t r0, int64_t r1, int32_t logCorrect, void *dOut, int64_t ld, void *out) {
+    if (!c) return VFT_ERR_INVALID;
+    if (!dOut) return fail(c, VFT_ERR_INVALID, "vft_seq_matrix_rows: d_out is NULL");
+    if (!c->leavesUp) return fail(c, VFT_ERR_STATE, "vft_seq_matrix_rows before vft_upload_leaves");
+    const int64_t n = c->d.nSeqs;
+    if (r0 < 0 || r0 >= r1 || r1 > n)
+        return fail(c, VFT_ERR_INVALID, "vft_seq_matrix_rows: rows [%lld, %lld) are not within [0, %lld)", (long long) r0, (long long) r1, (long long) n);
+    if (ld < n) return fail(c, VFT_ERR_INVALID, "vft_seq_matrix_rows: ld %lld is below n_seqs %lld", (long long) ld, (long long) n);
+    if (c->cfg.n_codes == 4 && c->hasDm)
+        return fail(c, VFT_ERR_INVALID, "vft_seq_matrix_rows: nucleotides with a distance matrix are not built (the reference's -makematrix has none either)");
+    if (c->cfg.n_codes != 4 && !c->hasDm)
+        return fail(c, VFT_ERR_INVALID, "vft_seq_matrix_rows: proteins need a distance matrix (vft_set_distance_matrix)");
+    const int64_t rowBlocks = (r1 - r0 + 63) / 64;
+    if (rowBlocks > 65535) return fail(c, VFT_ERR_INVALID, "vft_seq_matrix_rows: at most %lld rows per call", 65535ll * 64);
+    const dim3 grid(cdiv(n, 64), (unsigned) rowBlocks);
+    if (c->cfg.n_codes == 4) {
+        if (c->rs == 4) launch((k_seqmatrix_nt<float>), grid, dim3(VFT_SM_WG), 0, c->stream, (const uint4 *) c->leafT, c->d, r0, r1, logCorrect, (float *) dOut, ld);
+        else launch((k_seqmatrix_nt<double>), grid, dim3(VFT_SM_WG), 0, c->stream, (const uint4 *) c->leafT, c->d, r0, r1, logCorrect, (double *) dOut, ld);
+    } else {
+        if (c->rs == 4)
+            launch((k_seqmatrix_aa<float>), grid, dim3(VFT_SM_WG), 0, c->stream, (const uint4 *) c->leafT, c->d, (const float *) c->dm[0], r0, r1, logCorrect,
+                   (float *) dOut, ld);
+        else
+            launch((k_seqmatrix_aa<double>), grid, dim3(VFT_SM_WG), 0, c->stream, (const uint4 *) c->leafT, c->d, (const double *) c->dm[0], r0, r1, logCorrect,
+                   (double *) dOut, ld);
+    }
+    LAUNCHCHK(c);
+    if (out) {
+        HIPCHK(c, hipMemcpyAsync(out, dOut, (size_t) (r1 - r0) * (size_t) ld * c->rs, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     return VFT_OK;
 }
 

@@ -15,6 +15,7 @@
 #include "MLLengths.h"
 #include "GtrModel.h"
 #include "AAModels.h"
+#include "SeqMatrix.h"
 
 // CRC-32 (the zlib polynomial) of the last join order this process produced, per chunk of joins: lets a caller that only asked
 // for the tree (vft_nj_newick at a million sequences) compare the join order with a prefix of the reference's `Join` lines
@@ -475,6 +476,45 @@ extern "C" int vft_aa_model_as_distance_tables(int32_t model, int32_t precision,
         distanceTablesOut(d, distances, codefreq, eigenval, eigentot);
         return VFT_OK;
     } catch (const std::exception &) {
+        return VFT_ERR_INVALID;
+    }
+}
+
+template <typename REAL>
+static veryfasttree::SeqMatrixTimes runMakeMatrix(vft_ctx *ctx, int64_t nSeqs, const std::vector<std::string> &names, bool logCorrect,
+                                                  int64_t slabRows, int fd) {
+    veryfasttree::DeviceSlabs<REAL> slabs(ctx, nSeqs, slabRows, logCorrect);
+    return veryfasttree::writeSeqMatrix<REAL>(slabs, nSeqs, names, slabs.slabRows(), fd);
+}
+
+extern "C" int vft_nj_make_matrix(vft_ctx *ctx, int64_t nSeqs, int32_t precision, const char *names, int32_t logCorrect, int64_t slabRows,
+                                  int32_t fd, const vft_comm *comm, double *seconds, int64_t *counts, char *err, int32_t errLen) {
+    try {
+        if (!ctx || !names || nSeqs < 1 || fd < 0 || (precision != 4 && precision != 8)) throw std::runtime_error("vft_nj_make_matrix: bad arguments");
+        if (comm && comm->world > 1)
+            throw std::runtime_error("-makematrix runs on one GPU: the matrix is not split over the ranks of a communicator (and is not approximated)");
+        std::vector<std::string> nm;
+        const char *p = names;
+        for (int64_t k = 0; k < nSeqs; k++) {
+            nm.emplace_back(p);
+            p += nm.back().size() + 1;
+        }
+        const veryfasttree::SeqMatrixTimes T = precision == 4 ? runMakeMatrix<float>(ctx, nSeqs, nm, logCorrect != 0, slabRows, fd)
+                                                              : runMakeMatrix<double>(ctx, nSeqs, nm, logCorrect != 0, slabRows, fd);
+        if (seconds) {
+            seconds[0] = T.wait;
+            seconds[1] = T.format;
+            seconds[2] = T.write;
+            seconds[3] = T.total;
+        }
+        if (counts) {
+            counts[0] = T.slabs;
+            counts[1] = T.slabRows;
+            counts[2] = T.bytes;
+        }
+        return VFT_OK;
+    } catch (const std::exception &e) {
+        if (err && errLen > 0) snprintf(err, (size_t) errLen, "%s", e.what());
         return VFT_ERR_INVALID;
     }
 }
