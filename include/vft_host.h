@@ -112,6 +112,18 @@ typedef struct {
                                    byte.  Not built: -slow with me_nni, spr or ml_nni (the reference's updateForNNI, SPR and DoNNI
                                    behave differently under -slow, NJ.tcc:1883-1901, :6267-6284, :5980) and with a vft_comm of more
                                    than one rank - each an error, never the non-slow stage.  0 = everything above as before. */
+    const char *intree;         /* `-intree FILE` (readTree, NJ.tcc:2449-2704; VeryFastTreeImpl.tcc:124-143): NUL-terminated Newick text of a
+                                   starting tree, NULL = none (the last member: a zero-initialised caller keeps everything above).  The
+                                   NJ phase does not run: the text is parsed on the host (vft_read_tree below has the rules), every
+                                   internal node but the root becomes the unweighted average of its two children, all branch lengths
+                                   start at zero, and every later stage runs as after fastNJ - `-intree T -nome -mllen` re-estimates
+                                   lengths and supports on T, plain `-intree T` refines T.  vft_nj_newick and vft_nj_ml_newick honour it;
+                                   with me_lengths = 0 and no supports the printed tree is the reference's "NJ" log line of such a run
+                                   (all lengths 0.00000).  fastest and the top-hits numbers are ignored, as in the reference.
+                                   vft_nj_last_join_crcs reports zero joins; slot 0 of vft_nj_last_stage_seconds is the time to read the
+                                   tree and build the profiles.  Refused before anything reaches the device: vft_nj_run (it returns
+                                   joins), intree with slow (the NNI and SPR stages of a -slow run are not built), with a vft_comm of
+                                   more than one rank, with fewer than 4 unique sequences, and every tree vft_read_tree refuses. */
 } vft_nj_options;
 #define VFT_NJ_DEBUG_HOST_JOINS 1
 #define VFT_NJ_DEBUG_HOST_LISTS 2
@@ -171,6 +183,24 @@ int vft_nj_last_join_crcs(int64_t *chunk, int64_t *n_joins, uint32_t *crcs, int6
    their lanes from (penalty 2 / 1).  out[cap] may be NULL to query *n_out. */
 int vft_tree_partitioning(int64_t n_nodes, const int64_t *child, int64_t root, int32_t penalty, int32_t threads, int32_t window,
                           int64_t *out, int64_t cap, int64_t *n_out, double *speedup);
+
+/* The parse of `-intree` (NJ.tcc:2449-2665), pure host code (host/ReadTree.h): text = NUL-terminated Newick; names / unique_first / aln_next /
+   n_all / n_seqs as in vft_nj_newick.  Tokens: ( ) : ; , stand alone, white space ends a token, everything else accumulates (no quoting).
+   Branch lengths and numeric labels are dropped; any other label behind ')' is a warning.  A name is looked up among ALL names of the
+   alignment; the first occurrence of a unique sequence is its leaf, later ones (another name of the same sequence, the same name again) are
+   skipped.  Every unique sequence must occur.  Then internal nodes with fewer than two children are removed (their children go to the end
+   of the parent's list), a root with one child hands the root over, a root of two dissolves its first child of two.
+   Numbering: leaves keep their unique index; internal nodes get n_seqs, n_seqs + 1, ... in the order a stack pops them - the root first
+   (root == n_seqs, not the highest id as after the NJ phase), children pushed in list order, the last pushed popped first.
+   Out: parent[2 * n_seqs] (-1 at the root and behind n_nodes), child[2 * n_seqs][3] (-1 = none; list order), root, n_nodes = 2 n_seqs - 2;
+   warnings[warnings_cap] (may be NULL): the warning lines, each ended by a newline.
+   Errors carry the reference's texts ("Tree parse error: unexpected token '<tok>' -- <what>", "Alignment sequence .. absent from input
+   tree ..").  Where the reference has only asserts, this refuses: a node may never hold more than three children, and after the
+   simplification every internal node has two children and the root three - the message names the first leaf below the node.
+   No recursion and one hash map of the names: a caterpillar of 10^6 leaves is a legal input. */
+int vft_read_tree(const char *text, int64_t n_all, const char *names, const int64_t *unique_first, const int64_t *aln_next, int64_t n_seqs,
+                  int64_t *parent, int64_t *child, int64_t *root, int64_t *n_nodes, char *warnings, int64_t warnings_cap, char *err,
+                  int32_t err_len);
 
 /* Where the wall-clock of the last vft_nj_newick / vft_nj_ml_newick of this process went.  seconds[8]: the NJ phase with its root;
    the minimum-evolution NNI + SPR rounds, of which the SPR rounds; ME branch lengths + local supports; the whole ML stage, of which

@@ -7,6 +7,7 @@ or - with -mllen - the tree of `VeryFastTree -nt -nome -mllen [-nocat | -cat N] 
     python tools/nj_tree.py in.fasta -full [-gtr] [-double] [-nosupport] > tree.nwk     # what plain `VeryFastTree -nt [-gtr]` prints
     python tools/nj_tree.py in.fasta -full -lg -double > tree.nwk     # proteins: `VeryFastTree -lg -double-precision` (-aa / -jtt, -wag, -lg)
     python tools/nj_tree.py in.fasta -full -threads 64 [-gamma] [-spr N] > tree.nwk   # the schedule of `VeryFastTree -threads 64`; -gamma; -spr N rounds
+    python tools/nj_tree.py in.fasta -intree start.nwk [-mllen ... | -full ...] > tree.nwk   # `VeryFastTree -intree start.nwk ...`: no NJ phase
     python tools/nj_tree.py -makematrix [-rawdist] [-aa] [-double] in.fasta > matrix.txt   # `VeryFastTree [-nt] [-rawdist] [-double-precision] -makematrix`
 
 Neighbour joining with top hits on the device (veryfasttree_amd/host/NJDriver.h), the root, minimum-evolution branch
@@ -17,6 +18,10 @@ lengths on that topology (optimizeAllBranchLengths rounds, CAT rate categories u
 -slow: the exhaustive search of the reference's `-slow` (every join is the best pair of all active nodes, on a distance
 matrix kept on the device) instead of top hits; not together with -fastest (as in the reference) or -full (the NNI and
 SPR stages of a -slow run are not built).
+-intree FILE: the topology of FILE (Newick; branch lengths and labels in it are ignored, duplicate sequences may be named once or
+several times, every unique sequence at least once, binary apart from the root) replaces neighbour joining, as the reference's
+-intree does; each mode then runs as usual: default = ME lengths and local supports on that topology (`-intree T -noml -nome`),
+-mllen = ML lengths and SH-like supports on it (`-intree T -nome -mllen`), -full = refine it (`-intree T`).  Not with -slow.
 -makematrix: no tree - the log-corrected distance of every pair of input sequences, computed on the device and printed the
 way `VeryFastTree [-nt] [-rawdist] [-double-precision] -makematrix in.fasta` prints it (one row per sequence: its name, then
 " %f" per sequence; proteins with -aa: BLOSUM45 distances).  Every sequence is kept (no uniquify); repeated names are an
@@ -95,6 +100,16 @@ def main():
         sys.exit("-slow and -fastest exclude each other")
     if slow and "-full" in args:
         sys.exit("-slow with -full is not built: use -slow alone (the tree of -slow -noml -nome) or with -mllen")
+    intree = None
+    if "-intree" in args:
+        if slow:
+            sys.exit("-intree with -slow is not built")
+        k = args.index("-intree")
+        if k + 1 >= len(args):
+            sys.exit("-intree needs a file")
+        with open(args[k + 1]) as fh:
+            intree = fh.read()
+        del args[k:k + 2]
     mllen = 0
     if "-mllen" in args:
         mllen = 1 if "-nocat" in args else (int(args[args.index("-cat") + 1]) if "-cat" in args else 20)
@@ -138,9 +153,14 @@ def main():
     dt = np.float64 if double else np.float32
     if aa:
         extra["aa_model"] = aa
-    tree, loglk = nj_newick(lambda n, L: HipProfileOps(n, L, 20 if aa else 4, dt, max_nodes=3 * n), codes_all, names, fastest=fastest,
-                            dtype=dt, me_lengths=not nj_len, unique=(np.array(unique_first, np.int64), aln_next),
-                            n_bootstrap=n_boot, mllen=mllen, return_loglk=True, slow=slow, **extra)
+    try:
+        tree, loglk = nj_newick(lambda n, L: HipProfileOps(n, L, 20 if aa else 4, dt, max_nodes=3 * n), codes_all, names, fastest=fastest,
+                                dtype=dt, me_lengths=not nj_len, unique=(np.array(unique_first, np.int64), aln_next),
+                                n_bootstrap=n_boot, mllen=mllen, return_loglk=True, slow=slow, intree=intree, **extra)
+    except VftError as e:
+        if intree is None:
+            raise
+        sys.exit(str(e))
     for k, ll in enumerate(loglk):
         sys.stderr.write("TreeLogLk\t%s%d\t%.4f\n" % ("Round" if extra else "Length", k + 1, ll))
     print(tree)

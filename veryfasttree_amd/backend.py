@@ -60,7 +60,7 @@ class _NJOptions(C.Structure):
     _fields_ = [("fastest", I32), ("use_tophits_2nd", I32), ("tophits_mult", C.c_double), ("tophits_close", C.c_double),
                 ("tophits_refresh", C.c_double), ("topvisible_mult", C.c_double), ("stale_out_limit", C.c_double),
                 ("f_reset_out_profile", C.c_double), ("n_reset_out_profile", I32), ("tophits2_safety", I32),
-                ("tophits2_mult", C.c_double), ("tophits2_refresh", C.c_double), ("scoredist", I32), ("mllen", I32), ("me_nni", I32), ("ml_nni", I32), ("spr", I32), ("gtr", I32), ("aa_model", I32), ("comm", P), ("threads", I32), ("debug_flags", I32), ("gamma", I32), ("out_profile_parts", I32), ("slow", I32)]
+                ("tophits2_mult", C.c_double), ("tophits2_refresh", C.c_double), ("scoredist", I32), ("mllen", I32), ("me_nni", I32), ("ml_nni", I32), ("spr", I32), ("gtr", I32), ("aa_model", I32), ("comm", P), ("threads", I32), ("debug_flags", I32), ("gamma", I32), ("out_profile_parts", I32), ("slow", I32), ("intree", C.c_char_p)]
 
 
 class _ExhaustiveBest(C.Structure):
@@ -148,8 +148,9 @@ class TorchComm:
 
 
 def nj_run(ops, codes, fastest=False, max_joins=-1, tophits_refresh=None, second_level=None, scoredist=False, aa_model=None,
-           tophits_mult=1.0, comm=None, debug_flags=0, out_profile_parts=0, slow=False):
+           tophits_mult=1.0, comm=None, debug_flags=0, out_profile_parts=0, slow=False, intree=None):
     """fastNJ through the C++ host driver.  Returns (joins[n,3], criterion[n]).
+    intree: always refused - a run from a starting tree has no joins to return (vft_nj_options.intree).
     second_level defaults to `fastest`, as in the reference at one thread (-fastest turns -2nd on).
     slow: `-slow`, the exhaustive search over a device-resident distance matrix (vft_exhaustive_*)."""
     lib = load_host_library()
@@ -160,7 +161,8 @@ def nj_run(ops, codes, fastest=False, max_joins=-1, tophits_refresh=None, second
     opt = _NJOptions(1 if fastest else 0, 1 if second_level else 0, float(tophits_mult), -1.0,
                      tophits_refresh if tophits_refresh is not None else (0.5 if fastest else 0.8), 1.5, 0.01, 0.02,
                      200, 3, 1.0, 0.6, 1 if scoredist else 0, 0, 0, 0, 0, 0, AA_MODELS[aa_model],
-                     comm.pointer() if comm is not None else None, 1, int(debug_flags), 0, int(out_profile_parts), 1 if slow else 0)
+                     comm.pointer() if comm is not None else None, 1, int(debug_flags), 0, int(out_profile_parts), 1 if slow else 0,
+                     None if intree is None else _intree_bytes(intree))
     joins = np.zeros((max(n - 3, 1), 3), np.int64)
     crit = np.zeros(max(n - 3, 1), np.float64)
     nj = I64(0)
@@ -253,8 +255,9 @@ def uniquify(codes):
 
 def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtype=np.float32, me_lengths=False,
               unique=None, scoredist=False, n_bootstrap=0, mllen=0, return_loglk=False, return_rates=False, me_nni=False, ml_nni=0, spr=0, gtr=False, return_gtr=False,
-              aa_model=None, comm=None, threads=1, debug_flags=0, gamma=False, out_profile_parts=0, slow=False):
+              aa_model=None, comm=None, threads=1, debug_flags=0, gamma=False, out_profile_parts=0, slow=False, intree=None):
     """The NJ phase of the whole alignment `codes_all` (duplicates included) as the reference's "NJ" tree string.
+    intree (str): `-intree` - Newick text of a starting tree; the NJ phase does not run (vft_nj_options.intree).
     make_ops(n_unique, n_pos) -> HipProfileOps for the unique sequences (max_nodes >= 3 * n_unique with me_lengths:
     then the tree carries the minimum-evolution branch lengths, the final output of -noml -nome -nosupport)."""
     lib = load_host_library()
@@ -271,7 +274,8 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
         second_level = fastest
     opt = _NJOptions(1 if fastest else 0, 1 if second_level else 0, 1.0, -1.0, 0.5 if fastest else 0.8, 1.5, 0.01, 0.02,
                      200, 3, 1.0, 0.6, 1 if scoredist else 0, int(mllen), 1 if me_nni else 0, int(ml_nni), int(spr), 1 if gtr else 0,
-                     AA_MODELS[aa_model], comm.pointer() if comm is not None else None, int(threads), int(debug_flags), 1 if gamma else 0, int(out_profile_parts), 1 if slow else 0)
+                     AA_MODELS[aa_model], comm.pointer() if comm is not None else None, int(threads), int(debug_flags), 1 if gamma else 0, int(out_profile_parts), 1 if slow else 0,
+                     None if intree is None else _intree_bytes(intree))
     blob = b"".join(nm.encode() + b"\0" for nm in names)
     cap = 64 * len(names) + len(blob) + 1024
     out = C.create_string_buffer(cap)
@@ -296,6 +300,43 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
     if return_loglk:
         return out.value.decode(), loglk[:n_rounds.value]
     return out.value.decode()
+
+
+def _intree_bytes(text):
+    if not isinstance(text, str):
+        raise VftError("intree is the Newick text of the starting tree (a str)")
+    raw = text.encode()
+    if b"\0" in raw:
+        raise VftError("intree: the text holds a NUL character")
+    return raw
+
+
+def read_tree(text, names, codes_all, unique=None, return_warnings=False):
+    """The parse of `-intree` (vft_read_tree, host/ReadTree.h; no device): text = Newick, names / codes_all = the WHOLE alignment,
+    unique = (unique_first, aln_next) as in nj_newick (default: rows with equal codes are duplicates).
+    Returns (parent[n_nodes], child[n_nodes, 3], root) - leaves are the unique sequences 0 .. n-1, the root is node n -
+    and, with return_warnings, the list of warning lines."""
+    lib = load_host_library()
+    unique_first, aln_next = unique if unique is not None else uniquify(codes_all)
+    unique_first = np.ascontiguousarray(unique_first, np.int64)
+    aln_next = np.ascontiguousarray(aln_next, np.int64)
+    if len(names) != len(aln_next):
+        raise VftError("read_tree: %d names for %d sequences" % (len(names), len(aln_next)))
+    n = len(unique_first)
+    blob = b"".join(nm.encode() + b"\0" for nm in names)
+    parent = np.full(2 * n, -1, np.int64)
+    child = np.full((2 * n, 3), -1, np.int64)
+    root, n_nodes = I64(-1), I64(0)
+    warn = C.create_string_buffer(4096)
+    err = C.create_string_buffer(1024)
+    rc = lib.vft_read_tree(_intree_bytes(text), I64(len(names)), blob, _ptr(unique_first), _ptr(aln_next), I64(n), _ptr(parent), _ptr(child),
+                           C.byref(root), C.byref(n_nodes), warn, I64(4096), err, I32(1024))
+    if rc != 0:
+        raise VftError(err.value.decode() or "vft_read_tree failed")
+    out = (parent[:n_nodes.value], child[:n_nodes.value], int(root.value))
+    if return_warnings:
+        return out + (warn.value.decode().splitlines(),)
+    return out
 
 
 def make_matrix(codes_all, names, n_codes, dtype, rawdist, out_fd, slab_rows=None, comm=None, return_times=False):

@@ -553,6 +553,67 @@ namespace veryfasttree {
             chkT("vft_set_profile_rows", [&]() { return vft_set_profile_rows(ctx, 1); });
         }
 
+        /* `-intree` (readTree, NJ.tcc:2449-2704, after its parse - host/ReadTree.h): the second way to the state finishRoot() leaves.
+           par[nNodes] / ch[nNodes][3] as ReadTree numbers them: leaves 0 .. nSeqs-1, the root = nSeqs with three children, every other
+           internal node two, nNodes = 2 nSeqs - 2.  All branch lengths stay zero and no join is logged; every internal node but the root
+           becomes the unweighted average of its two children (setProfile(node, -1), NJ.tcc:2695-2701), bottom-up as one
+           vft_average_profiles per height - written as plain rows, the layout everything after the NJ phase works on.  Nothing on the
+           device is left from a join loop: diameters, out-distances and parents of internal nodes are never read behind this point. */
+        void readTree(const int64_t *par, const int64_t *ch, int64_t rootIn, int64_t nNodes) {
+            if (root >= 0 || maxnode != nSeqs) throw std::invalid_argument("NJDriver::readTree: the driver already holds a tree");
+            if (nSeqs < 4) throw std::invalid_argument("NJDriver::readTree: fewer than 4 unique sequences");
+            if (nNodes != 2 * nSeqs - 2 || rootIn < nSeqs || rootIn >= nNodes) throw std::invalid_argument("NJDriver::readTree: not a binary tree with a root of three");
+            /* a tree, so that the walks below end and stay inside the arrays: every node but the root is the child of its parent once */
+            std::vector<char> seen((size_t) nNodes, 0);
+            for (int64_t v = nSeqs; v < nNodes; v++) {
+                const int want = v == rootIn ? 3 : 2;
+                for (int k = 0; k < 3; k++) {
+                    const int64_t c = ch[3 * v + k];
+                    if (k >= want ? c != -1 : (c < 0 || c >= nNodes || c == rootIn || seen[(size_t) c] || par[c] != v))
+                        throw std::invalid_argument("NJDriver::readTree: inconsistent tree arrays");
+                    if (c >= 0) seen[(size_t) c] = 1;
+                }
+            }
+            for (int64_t v = 0; v < nNodes; v++)
+                if (v != rootIn && !seen[(size_t) v]) throw std::invalid_argument("NJDriver::readTree: a node without a parent");
+            for (int64_t v = 0; v < nNodes; v++) {
+                parent[(size_t) v] = v == rootIn ? -1 : par[v];
+                if (v >= nSeqs && v != rootIn) {
+                    child0[(size_t) v] = ch[3 * v];
+                    child1[(size_t) v] = ch[3 * v + 1];
+                }
+            }
+            root = rootIn;
+            for (int k = 0; k < 3; k++) rootChild[k] = ch[3 * root + k];
+            maxnode = nNodes;
+            /* heights from the leaves up: a node is ready once both children are (no recursion: a caterpillar is a legal tree) */
+            std::vector<int64_t> height((size_t) nNodes, 0), waiting((size_t) nNodes, 0), ready;
+            for (int64_t v = nSeqs; v < nNodes; v++) waiting[(size_t) v] = v == root ? 3 : 2;
+            for (int64_t v = 0; v < nSeqs; v++) ready.push_back(v);
+            std::vector<std::vector<int64_t> > byHeight;
+            for (size_t t = 0; t < ready.size(); t++) {
+                const int64_t v = ready[t], p = parent[(size_t) v];
+                if (p < 0 || p == root) continue;
+                height[(size_t) p] = std::max(height[(size_t) p], height[(size_t) v] + 1);
+                if (--waiting[(size_t) p] == 0) {
+                    if ((int64_t) byHeight.size() <= height[(size_t) p]) byHeight.resize((size_t) height[(size_t) p] + 1);
+                    byHeight[(size_t) height[(size_t) p]].push_back(p);
+                    ready.push_back(p);
+                }
+            }
+            chkT("vft_set_profile_rows", [&]() { return vft_set_profile_rows(ctx, 1); });   /* no internal profile exists yet: nothing to move */
+            chkT("vft_set_max_node", [&]() { return vft_set_max_node(ctx, maxnode); });
+            for (const std::vector<int64_t> &out: byHeight) {
+                if (out.empty()) continue;
+                std::vector<int64_t> a, b;
+                for (int64_t v: out) {
+                    a.push_back(child0[(size_t) v]);
+                    b.push_back(child1[(size_t) v]);
+                }
+                chkT("vft_average_profiles", [&]() { return vft_average_profiles(ctx, (int64_t) out.size(), out.data(), a.data(), b.data(), nullptr); });
+            }
+        }
+
         /* up-profiles of all internal nodes on the device (node X -> id X + nSeqs), breadth first from the root:
            one vft_average_profiles per depth (getUpProfile, NJ.tcc:3382-3434, useML = false, -nj weighting) */
         void ensureUpProfiles() {

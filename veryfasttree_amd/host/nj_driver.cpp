@@ -16,6 +16,7 @@
 #include "GtrModel.h"
 #include "AAModels.h"
 #include "SeqMatrix.h"
+#include "ReadTree.h"
 
 // CRC-32 (the zlib polynomial) of the last join order this process produced, per chunk of joins: lets a caller that only asked
 // for the tree (vft_nj_newick at a million sequences) compare the join order with a prefix of the reference's `Join` lines
@@ -205,6 +206,72 @@ static veryfasttree::NJOptions toOptions(const vft_nj_options *o) {
     return opt;
 }
 
+/* the description of duplicates vft_nj_newick takes (unique_first / aln_next) as the alignment row -> unique sequence map */
+static std::vector<int64_t> alnToUnique(const int64_t *uniqueFirst, const int64_t *alnNext, int64_t nSeqs, int64_t nAll) {
+    std::vector<int64_t> out((size_t) nAll, -1);
+    for (int64_t u = 0; u < nSeqs; u++)
+        for (int64_t k = uniqueFirst[u]; k != -1; k = alnNext[k]) {
+            if (k < 0 || k >= nAll || out[(size_t) k] >= 0) throw std::invalid_argument("unique_first / aln_next do not describe the alignment's duplicates");
+            out[(size_t) k] = u;
+        }
+    for (int64_t k = 0; k < nAll; k++)
+        if (out[(size_t) k] < 0) throw std::invalid_argument("unique_first / aln_next leave an alignment row without a unique sequence");
+    return out;
+}
+
+static std::vector<std::string> splitNames(const char *names, int64_t nAll) {
+    std::vector<std::string> nm;
+    nm.reserve((size_t) nAll);
+    const char *p = names;
+    for (int64_t k = 0; k < nAll; k++) {
+        nm.push_back(std::string(p));
+        p += nm.back().size() + 1;
+    }
+    return nm;
+}
+
+static veryfasttree::ReadTreeResult readTreeText(const char *text, int64_t nAll, const char *names, const int64_t *uniqueFirst,
+                                                 const int64_t *alnNext, int64_t nSeqs) {
+    if (!text || !names || !uniqueFirst || !alnNext || nSeqs < 1 || nAll < nSeqs) throw std::invalid_argument("vft_read_tree: bad arguments");
+    const std::vector<std::string> nm = splitNames(names, nAll);
+    return veryfasttree::ReadTree::parse(text, strlen(text), nm, alnToUnique(uniqueFirst, alnNext, nSeqs, nAll),
+                                         std::vector<int64_t>(uniqueFirst, uniqueFirst + nSeqs));
+}
+
+/* the parse of `-intree` alone (host/ReadTree.h): pure host code, no context */
+extern "C" int vft_read_tree(const char *text, int64_t nAll, const char *names, const int64_t *uniqueFirst, const int64_t *alnNext,
+                             int64_t nSeqs, int64_t *parent, int64_t *child, int64_t *root, int64_t *nNodes, char *warnings,
+                             int64_t warningsCap, char *err, int32_t errLen) {
+    try {
+        if (!parent || !child || !root || !nNodes) throw std::invalid_argument("vft_read_tree: bad arguments");
+        const veryfasttree::ReadTreeResult r = readTreeText(text, nAll, names, uniqueFirst, alnNext, nSeqs);
+        for (int64_t v = 0; v < 2 * nSeqs; v++) {
+            parent[v] = v < r.nNodes ? r.parent[(size_t) v] : -1;
+            for (int k = 0; k < 3; k++) child[3 * v + k] = v < r.nNodes ? r.child[(size_t) (3 * v + k)] : -1;
+        }
+        *root = r.root;
+        *nNodes = r.nNodes;
+        if (warnings && warningsCap > 0) {
+            std::string w;
+            for (const std::string &line: r.warnings) w += line + "\n";
+            snprintf(warnings, (size_t) warningsCap, "%s", w.c_str());
+        }
+        return VFT_OK;
+    } catch (const std::exception &e) {
+        if (err && errLen > 0) snprintf(err, (size_t) errLen, "%s", e.what());
+        return VFT_ERR_INVALID;
+    }
+}
+
+/* `-intree`: what is not built is refused before anything reaches the device (include/vft_host.h, vft_nj_options.intree) */
+static void checkIntree(const vft_nj_options *o, int64_t nSeqs) {
+    if (!o || !o->intree) return;
+    if (o->slow) throw std::invalid_argument("-intree with -slow is not built: the reference's NNI and SPR stages behave differently under -slow "
+                                             "(NJ.tcc:1883-1901, 5980, 6267-6284), and the option's own stage, the exhaustive join search, does not run with a starting tree");
+    if (o->comm && o->comm->world > 1) throw std::invalid_argument("-intree with a vft_comm of more than one rank is not built");
+    if (nSeqs < 4) throw std::invalid_argument("-intree needs at least 4 unique sequences");
+}
+
 /* `-slow`: what is not built is refused before anything reaches the device (include/vft_host.h, vft_nj_options.slow) */
 static void checkSlow(const vft_nj_options *o) {
     if (!o || !o->slow) return;
@@ -220,13 +287,22 @@ static std::string runTree(vft_ctx *ctx, const uint8_t *codes, int64_t nSeqs, in
                            bool meLengths, int32_t nBootstrap, const int64_t *uniqueFirst, const int64_t *alnNext,
                            int64_t nAll, const char *names, std::vector<double> &loglk, std::vector<double> &rates,
                            std::vector<int64_t> &ratecat, double *gtrOut) {
+    /* `-intree`: the text is parsed before anything reaches the device - a malformed tree costs no upload */
+    veryfasttree::ReadTreeResult tree;
+    if (o && o->intree) tree = readTreeText(o->intree, nAll, names, uniqueFirst, alnNext, nSeqs);
     veryfasttree::NJDriver<REAL> drv(ctx, codes, nSeqs, nPos, toOptions(o));
     for (double &x: gStage) x = 0;
     auto now = []() { return std::chrono::steady_clock::now(); };
     auto since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(now() - t).count(); };
     std::chrono::steady_clock::time_point t0 = now();
-    recordJoinCrc(drv.run(-1));
-    drv.finishRoot();
+    if (o && o->intree) {   /* `-intree`: the topology is given, fastNJ does not run (VeryFastTreeImpl.tcc:124-141) */
+        for (const std::string &w: tree.warnings) fprintf(stderr, "%s\n", w.c_str());
+        drv.readTree(tree.parent.data(), tree.child.data(), tree.root, tree.nNodes);
+        recordJoinCrc(drv.joins);   /* none */
+    } else {
+        recordJoinCrc(drv.run(-1));
+        drv.finishRoot();
+    }
     gStage[0] = since(t0);
     static const bool stageTrace = std::getenv("VFT_STAGE_TRACE") != nullptr;   /* tools: the stages as they end, on stderr */
     if (stageTrace) fprintf(stderr, "[stage] NJ phase done after %.1f s\n", gStage[0]);
@@ -267,12 +343,7 @@ static std::string runTree(vft_ctx *ctx, const uint8_t *codes, int64_t nSeqs, in
     gLaneExchange[0] = drv.laneGathers;
     gLaneExchange[1] = drv.laneGatherBytes;
     drv.report();
-    std::vector<std::string> nm;
-    const char *p = names;
-    for (int64_t k = 0; k < nAll; k++) {
-        nm.push_back(std::string(p));
-        p += nm.back().size() + 1;
-    }
+    const std::vector<std::string> nm = splitNames(names, nAll);
     return drv.newick(nm, std::vector<int64_t>(uniqueFirst, uniqueFirst + nSeqs), std::vector<int64_t>(alnNext, alnNext + nAll));
 }
 
@@ -283,6 +354,7 @@ extern "C" int vft_nj_ml_newick(vft_ctx *ctx, const uint8_t *codes, int64_t nSeq
                                 int32_t ratesCap, int32_t *nRates, int32_t *ratecatOut, double *gtrOut, char *err, int32_t errLen) {
     if (!ctx || !codes || !uniqueFirst || !alnNext || !names || !outLen) return VFT_ERR_INVALID;
     try {
+        checkIntree(opt, nSeqs);
         checkSlow(opt);
         std::vector<double> ll, rates;
         std::vector<int64_t> ratecat;
@@ -345,6 +417,7 @@ extern "C" int vft_nj_run(vft_ctx *ctx, const uint8_t *codes, int64_t nSeqs, int
                           int64_t *nJoins, char *err, int32_t errLen) {
     if (!ctx || !codes || !joins || !nJoins) return VFT_ERR_INVALID;
     try {
+        if (opt && opt->intree) throw std::invalid_argument("vft_nj_run returns the joins of the NJ phase: with -intree there are none (use vft_nj_newick)");
         checkSlow(opt);
         *nJoins = precision == 8 ? runDriver<double>(ctx, codes, nSeqs, nPos, opt, maxJoins, joins, criterion)
                                  : runDriver<float>(ctx, codes, nSeqs, nPos, opt, maxJoins, joins, criterion);
