@@ -533,7 +533,10 @@ int vft_ml_eval_count(vft_ctx *ctx, int64_t *evals);
 
 /* Local-bootstrap supports (splitSupport, NJ.tcc:607-702) of n splits (a[k], b[k]) | (c[k], d[k]): col holds n_boot
    resamples of n_pos column indices each ([n_boot][n_pos], host; resampleColumns NJ.tcc:705-727); support[k] = the
-   fraction of resamples in which the split beats both alternative pairings of the four profiles. */
+   fraction of resamples in which the split beats both alternative pairings of the four profiles.  Any alignment the NJ
+   phase takes (up to 10 240 columns): up to 1 706 columns one kernel holds the six pairs of a quartet in LDS, beyond
+   that another takes them in passes of 3, 2 or 1 pairs (the same sums, the same supports); longer alignments are
+   refused with VFT_ERR_INVALID before any launch. */
 int vft_split_supports(vft_ctx *ctx, int64_t n, const int64_t *a, const int64_t *b, const int64_t *c, const int64_t *d,
                        int32_t n_boot, const int32_t *col, double *support);
 
@@ -555,6 +558,7 @@ int vft_debug_log(vft_ctx *ctx, int64_t n, const double *x, double *out);
 #define VFT_DEBUG_WALK_SERVER_STRIDE 11 /* 1: the server's six workgroups on six XCDs instead of one (placement is for speed only; tests run both) */
 #define VFT_DEBUG_POISON_SELECTION 14    /* fills the selection's candidate buffers of every slot with 0x7f bytes - what a recycled allocation holds - before the next sweep (tests: a collection that overflows must not look at entries it never stored) */
 #define VFT_DEBUG_ML_LONG 16            /* value != 0: the ML line searches (vft_ml_optimize_splits, vft_ml_quartet_nni*, vft_ml_split_tests) run the workspace kernels of alignments beyond 2 048 columns at any length (tests compare with the register-resident kernels) */
+#define VFT_DEBUG_SUPPORT_PAIRS 17       /* 1, 2, 3: vft_split_supports runs the pass kernel of alignments beyond 1 706 columns (k_split_support_long) with that many pairs per pass at any length that fits (tests compare with the one-pass kernel); 0: the built-in choice */
 #define VFT_DEBUG_NO_MULTI_SWEEP 12     /* 1: vft_sweep_batch sweeps its seeds one launch each instead of four per pass over the targets (tests compare); 2 / 4: that many seeds per pass whatever the shard; 8: the per-kind passes stay but a group of leaf seeds and a group of profile seeds no longer share one (k_sweep_nt_mixed_multi off); 0: the built-in choice */
 int vft_debug_option(vft_ctx *ctx, int32_t option, int64_t value);
 

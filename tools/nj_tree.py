@@ -2,7 +2,7 @@
 """FASTA (nucleotides) -> Newick on one MI355X: the tree `VeryFastTree -nt [-fastest] -noml -nome [-nosupport]` prints,
 or - with -mllen - the tree of `VeryFastTree -nt -nome -mllen [-nocat | -cat N] [-nosupport]` (Jukes-Cantor).
 
-    python tools/nj_tree.py in.fasta [-fastest] [-double] [-nosupport] [-nj-lengths] [-mllen [-nocat | -cat N]] > tree.nwk
+    python tools/nj_tree.py in.fasta [-fastest] [-double] [-boot N | -nosupport] [-nj-lengths] [-mllen [-nocat | -cat N]] > tree.nwk
     python tools/nj_tree.py in.fasta -slow [-double] [-nosupport] [-nj-lengths] [-mllen [-nocat | -cat N]] > tree.nwk   # `VeryFastTree -slow ...`
     python tools/nj_tree.py in.fasta -full [-gtr] [-double] [-nosupport] > tree.nwk     # what plain `VeryFastTree -nt [-gtr]` prints
     python tools/nj_tree.py in.fasta -full -lg -double > tree.nwk     # proteins: `VeryFastTree -lg -double-precision` (-aa / -jtt, -wag, -lg)
@@ -26,6 +26,8 @@ several times, every unique sequence at least once, binary apart from the root) 
 way `VeryFastTree [-nt] [-rawdist] [-double-precision] -makematrix in.fasta` prints it (one row per sequence: its name, then
 " %f" per sequence; proteins with -aa: BLOSUM45 distances).  Every sequence is kept (no uniquify); repeated names are an
 error; not together with any tree option.
+-boot N: N resamples instead of 1000 for the supports, local (default mode) and SH-like (-mllen, -full) alike, as the reference's
+-boot; -boot 0 is -nosupport.  Local supports take every alignment the NJ phase takes (10 240 columns).
 Sequence normalisation and uniquify follow Alignment.cpp:453-526 (U -> T, '.' -> '-', duplicates by sequence string in
 first-occurrence order; N -> X for nucleotides)."""
 import os, sys
@@ -63,6 +65,22 @@ def codes_of(seqs, aa):
     for i, ch in enumerate(ALPHABET_AA if aa else ALPHABET_NT):
         lut[ord(ch)] = i
     return seqs, np.stack([lut[np.frombuffer(s.encode("ascii", "replace"), np.uint8)] for s in seqs])
+
+
+def parse_boot(args, nj_len=False):
+    """the number of resamples of the supports: `-boot N` (N >= 0; 0 = -nosupport), -nosupport / -nj-lengths 0, else 1000"""
+    n_boot = 1000
+    if "-boot" in args:
+        k = args.index("-boot")
+        if k + 1 >= len(args):
+            sys.exit("-boot needs a number of resamples")
+        try:
+            n_boot = int(args[k + 1])
+        except ValueError:
+            sys.exit("-boot needs a whole number of resamples, not '%s'" % args[k + 1])
+        if n_boot < 0:
+            sys.exit("-boot needs a number of resamples >= 0")
+    return 0 if ("-nosupport" in args or nj_len) else n_boot
 
 
 MAKEMATRIX_FLAGS = ("-makematrix", "-rawdist", "-aa", "-double")
@@ -113,7 +131,7 @@ def main():
     mllen = 0
     if "-mllen" in args:
         mllen = 1 if "-nocat" in args else (int(args[args.index("-cat") + 1]) if "-cat" in args else 20)
-    n_boot = 0 if ("-nosupport" in args or nj_len) else 1000
+    n_boot = parse_boot(args, nj_len)
     extra = dict(me_nni=True, spr=2, ml_nni=20) if "-full" in args else {}
     if "-gtr" in args:
         extra["gtr"] = True   # ME NNIs + SPRs, ML NNIs, CAT, SH supports

@@ -887,6 +887,15 @@ class HipProfileOps:
         nu = int(info[0])
         return dict(n_unique=nu, use_unique=bool(info[1]), n_save=int(info[2]), j=j[:nu], dist=d[:nu], criterion=cr[:nu])
 
+    def split_supports(self, a, b, c, d, col):
+        """vft_split_supports: local-bootstrap support of the splits (a[k], b[k]) | (c[k], d[k]) of node ids whose profiles are on
+        the device; col = int32 [n_boot][n_pos] column resamples.  Returns the fraction of supporting resamples per split."""
+        a, b, c, d = (np.ascontiguousarray(x, np.int64) for x in (a, b, c, d))
+        col = np.ascontiguousarray(col, np.int32)
+        out = np.zeros(len(a), np.float64)
+        self._chk(self.lib.vft_split_supports(self.ctx, I64(len(a)), _ptr(a), _ptr(b), _ptr(c), _ptr(d), I32(col.shape[0]), _ptr(col), _ptr(out)))
+        return out
+
     def debug_option(self, option, value):
         """test hook (include/vft_hip.h VFT_DEBUG_*): 1 no fused refresh, 2 threads per pair, 3 no pair staging, 4 generic out-profile"""
         self._chk(self.lib.vft_debug_option(self.ctx, C.c_int32(option), I64(value)))

@@ -71,6 +71,7 @@ struct vft_ctx {
     bool wideGlue = false;         // test hook: the 1 024-thread instance of k_nj_glue_scan at any size
     bool jcExact = true;           // vft_set_jc_exact: Jukes-Cantor likelihoods bit for bit the reference's (glibc exp, ordered totals) - the default
     bool mlLong = false;           // test hook: the line searches through the workspace kernels (vft_kernels_ml_long.h) at any length
+    int supportPairs = 0;          // test hook: vft_split_supports through k_split_support_long with this many pairs per pass at any length (0: by length)
     char *mlLongWs = nullptr;      // their workspaces (one per workgroup of a launch)
     size_t mlLongWsBytes = 0;
     size_t shLdsSet = 0;           // the largest dynamic LDS k_sh_support has been configured for
@@ -4444,8 +4445,19 @@ extern "C" int vft_split_supports(vft_ctx *c, int64_t n, const int64_t *a, const
             d[k] >= c->maxnode)
             return fail(c, VFT_ERR_INVALID, "vft_split_supports: quartet %lld out of range", (long long) k);
     const int64_t nPos = c->d.nPos;
-    const size_t lds = (size_t) 12 * nPos * sizeof(double);
-    if (lds > (160u << 10)) return fail(c, VFT_ERR_INVALID, "vft_split_supports: alignment too long (%lld columns, limit 1706)", (long long) nPos);
+    // k_split_support holds all six pairs (12 doubles per column, and its 4-byte counter) while the launch fits the 160 KB of
+    // LDS: up to 1 706 columns.  Beyond that k_split_support_long takes the pairs in passes of P, the largest P whose
+    // P x nPos double2 fit (3 up to 3 413 columns, 2 up to 5 120, 1 up to 10 240: the NJ phase's own limit).
+    const size_t ldsMax = 160u << 10;
+    int pairs = c->supportPairs;   // 0: the built-in choice
+    if (!pairs && (size_t) 12 * nPos * sizeof(double) + sizeof(unsigned int) > ldsMax) {
+        pairs = 3;
+        while (pairs > 1 && (size_t) pairs * nPos * sizeof(double2) > ldsMax) pairs--;
+    }
+    const size_t lds = pairs ? (size_t) pairs * nPos * sizeof(double2) : (size_t) 12 * nPos * sizeof(double);
+    if (lds > ldsMax)
+        return fail(c, VFT_ERR_INVALID, "vft_split_supports: alignment too long (%lld columns, limit %d)", (long long) nPos,
+                    (int) (ldsMax / sizeof(double2) / (pairs ? pairs : 1)));
     // the resample table, transposed to [nPos][nBoot]
     std::vector<int32_t> colT((size_t) nPos * nBoot);
     for (int32_t r = 0; r < nBoot; r++)
@@ -4472,8 +4484,13 @@ extern "C" int vft_split_supports(vft_ctx *c, int64_t n, const int64_t *a, const
     // a distance is < 3, so errors of a few 1e-16 cannot reach 1e-9
     const double eps = 1e-9;
     VFT_DISPATCH(c, {
-        if (lds > (48u << 10))
-            HIPCHK(c, hipFuncSetAttribute((const void *) k_split_support<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+        if (lds > (48u << 10)) {
+            const void *fn = pairs == 3   ? (const void *) k_split_support_long<REAL, NC, 3>
+                             : pairs == 2 ? (const void *) k_split_support_long<REAL, NC, 2>
+                             : pairs == 1 ? (const void *) k_split_support_long<REAL, NC, 1>
+                                          : (const void *) k_split_support<REAL, NC>;
+            HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+        }
     });
     std::vector<unsigned int> cnt((size_t) chunk);
     std::vector<double> rec;
@@ -4484,10 +4501,18 @@ extern "C" int vft_split_supports(vft_ctx *c, int64_t n, const int64_t *a, const
         HIPCHK(c, hipMemcpyAsync(s + 2 * idB, cc + k0, (size_t) m * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(s + 3 * idB, d + k0, (size_t) m * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemsetAsync(dNFlag, 0, 4, c->stream));
-        VFT_DISPATCH(c, (launch((k_split_support<REAL, NC>), dim3((unsigned) m), dim3(VFT_SUPPORT_WG), lds, c->stream,
-                                arena<REAL>(c), (const int64_t *) s, (const int64_t *) (s + idB), (const int64_t *) (s + 2 * idB),
-                                (const int64_t *) (s + 3 * idB), m, (const int32_t *) (s + 4 * idB), nBoot, scoredist, eps, dCnt,
-                                dNFlag, dFlag, flagCap)));
+        if (pairs) HIPCHK(c, hipMemsetAsync(dCnt, 0, (size_t) m * 4, c->stream));   // the long kernel adds to its counts
+#define VFT_SUPPORT_LAUNCH(KERNEL, WG)                                                                                        \
+    launch((KERNEL), dim3((unsigned) m), dim3(WG), lds, c->stream, arena<REAL>(c), (const int64_t *) s,                        \
+           (const int64_t *) (s + idB), (const int64_t *) (s + 2 * idB), (const int64_t *) (s + 3 * idB), m,                   \
+           (const int32_t *) (s + 4 * idB), nBoot, scoredist, eps, dCnt, dNFlag, dFlag, flagCap)
+        VFT_DISPATCH(c, {
+            if (pairs == 3) VFT_SUPPORT_LAUNCH((k_split_support_long<REAL, NC, 3>), VFT_SUPPORT_LONG_WG);
+            else if (pairs == 2) VFT_SUPPORT_LAUNCH((k_split_support_long<REAL, NC, 2>), VFT_SUPPORT_LONG_WG);
+            else if (pairs == 1) VFT_SUPPORT_LAUNCH((k_split_support_long<REAL, NC, 1>), VFT_SUPPORT_LONG_WG);
+            else VFT_SUPPORT_LAUNCH((k_split_support<REAL, NC>), VFT_SUPPORT_WG);
+        });
+#undef VFT_SUPPORT_LAUNCH
         LAUNCHCHK(c);
         unsigned int nFlag = 0;
         HIPCHK(c, hipMemcpyAsync(cnt.data(), dCnt, (size_t) m * 4, hipMemcpyDeviceToHost, c->stream));
@@ -4532,6 +4557,10 @@ extern "C" int vft_debug_option(vft_ctx *c, int32_t option, int64_t value) {
         case VFT_DEBUG_WAIT_LIMIT_MS: c->waitLimitS = value > 0 ? (double) value / 1000.0 : 120.0; break;
         case VFT_DEBUG_WIDE_GLUE: c->wideGlue = value != 0; break;
         case VFT_DEBUG_ML_LONG: c->mlLong = value != 0; break;
+        case VFT_DEBUG_SUPPORT_PAIRS:
+            if (value < 0 || value > 3) return fail(c, VFT_ERR_INVALID, "vft_debug_option: VFT_DEBUG_SUPPORT_PAIRS takes 0, 1, 2 or 3");
+            c->supportPairs = (int) value;
+            break;
         case VFT_DEBUG_NO_WALK_SERVER: c->ws.disabled = value != 0; break;
         case VFT_DEBUG_WALK_DEVICE_MAILBOX: c->ws.wantDeviceMail = value != 0; break;
         case VFT_DEBUG_WALK_SERVER_STRIDE: c->ws.stride = value == 1 ? 1 : 8; break;

@@ -969,6 +969,36 @@ __global__ __launch_bounds__(OpThreads<NC>::value) void k_outprofile_chain(Arena
 // equal the reference's exactly.  counts[k] = resamples decided "supported" on the device.
 #define VFT_SUPPORT_WG 256
 #define VFT_SUPPORT_REC 7   // doubles per flagged record
+
+// One resample's decision from its six uncorrected distances raw[j] = totw > 0.01 ? totp / totw : 3.0 (qAB, qAC, qAD, qBC,
+// qBD, qCD): true = supported, decided here; a near-tie goes to `flagged` for the host and counts as not decided.
+// Shared by k_split_support and k_split_support_long, so that both hand the host the same records.
+__device__ __forceinline__ bool vft_support_decide(const double (&raw)[6], int64_t k, int32_t scoredist, double eps,
+                                                   unsigned int *nFlagged, double *flagged, unsigned int flagCap) {
+    double d[6];
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double x = raw[j];
+        // logCorrect, NJ.tcc:322-330
+        if (scoredist) x = x < 0.99 ? -1.3 * log(1.0 - x) : 3.0;
+        else x = x < 0.74 ? -0.75 * log(1.0 - x * 4.0 / 3.0) : 3.0;
+        d[j] = x < 3.0 ? x : 3.0;
+    }
+    const double support1 = d[1] + d[4] - d[0] - d[5];   // AC + BD - AB - CD
+    const double support2 = d[2] + d[3] - d[0] - d[5];   // AD + BC - AB - CD
+    if (fabs(support1) < eps || fabs(support2) < eps) {
+        const unsigned int slot = atomicAdd(nFlagged, 1u);
+        if (slot < flagCap) {
+            double *rec = flagged + (size_t) slot * VFT_SUPPORT_REC;
+            rec[0] = (double) k;
+#pragma unroll
+            for (int j = 0; j < 6; j++) rec[1 + j] = raw[j];
+        }
+        return false;
+    }
+    return support1 > 0 && support2 > 0;
+}
+
 template <typename REAL, int NC>
 __global__ __launch_bounds__(VFT_SUPPORT_WG) void k_split_support(Arena<REAL> A, const int64_t *nA, const int64_t *nB,
                                                                   const int64_t *nC, const int64_t *nD, int64_t n,
@@ -1010,30 +1040,123 @@ __global__ __launch_bounds__(VFT_SUPPORT_WG) void k_split_support(Arena<REAL> A,
                 totw[j] += sW[j * nPos + col];
             }
         }
-        double raw[6], d[6];
+        double raw[6];
 #pragma unroll
-        for (int j = 0; j < 6; j++) {
-            double x = totw[j] > 0.01 ? totp[j] / totw[j] : 3.0;
-            raw[j] = x;
-            // logCorrect, NJ.tcc:322-330
-            if (scoredist) x = x < 0.99 ? -1.3 * log(1.0 - x) : 3.0;
-            else x = x < 0.74 ? -0.75 * log(1.0 - x * 4.0 / 3.0) : 3.0;
-            d[j] = x < 3.0 ? x : 3.0;
-        }
-        const double support1 = d[1] + d[4] - d[0] - d[5];   // AC + BD - AB - CD
-        const double support2 = d[2] + d[3] - d[0] - d[5];   // AD + BC - AB - CD
-        if (fabs(support1) < eps || fabs(support2) < eps) {
-            const unsigned int slot = atomicAdd(nFlagged, 1u);
-            if (slot < flagCap) {
-                double *rec = flagged + (size_t) slot * VFT_SUPPORT_REC;
-                rec[0] = (double) k;
-#pragma unroll
-                for (int j = 0; j < 6; j++) rec[1 + j] = raw[j];
-            }
-        } else if (support1 > 0 && support2 > 0) {
-            atomicAdd(&nSupport, 1u);
-        }
+        for (int j = 0; j < 6; j++) raw[j] = totw[j] > 0.01 ? totp[j] / totw[j] : 3.0;
+        if (vft_support_decide(raw, k, scoredist, eps, nFlagged, flagged, flagCap)) atomicAdd(&nSupport, 1u);
     }
     __syncthreads();
     if (threadIdx.x == 0) counts[k] = nSupport;
+}
+
+// The same for alignments whose 12 per-column arrays do not fit the LDS (beyond 1 706 columns): a resample needs every
+// column of a pair, but only of the pairs it is summing, so the workgroup takes the six pairs in passes of P (3, 2 or 1)
+// and restages {piece, weight} of the pass's pairs - P x nPos double2, at most 160 KB - before each.  A thread owns one
+// resample per block of blockDim resamples and keeps the quotients of the finished passes in registers; the pieces, the
+// order of the sums (sample order, double) and the decision (vft_support_decide) are k_split_support's, so the counts are.
+// No static LDS (at P = 1 and 10 240 columns the dynamic part is the whole 160 KB): the supported resamples are counted per
+// wavefront by ballot and added to counts[k], which the caller zeroes before the launch.
+#define VFT_SUPPORT_LONG_WG 1024
+template <typename REAL, int NC, int P>
+__global__ __launch_bounds__(VFT_SUPPORT_LONG_WG) void k_split_support_long(Arena<REAL> A, const int64_t *nA, const int64_t *nB,
+                                                                            const int64_t *nC, const int64_t *nD, int64_t n,
+                                                                            const int32_t *colT, int32_t nBoot, int32_t scoredist,
+                                                                            double eps, unsigned int *counts,
+                                                                            unsigned int *nFlagged, double *flagged,
+                                                                            unsigned int flagCap) {
+    static_assert(P == 1 || P == 2 || P == 3, "pairs per pass");
+    extern __shared__ __attribute__((aligned(16))) double2 spLong[];   // [P][nPos] {weighted piece, weight}
+    const int64_t k = blockIdx.x;
+    if (k >= n) return;
+    const int32_t nPos = (int32_t) A.d.nPos;
+    const int64_t q[4] = {nA[k], nB[k], nC[k], nD[k]};
+    unsigned int nSupport = 0;   // lane 0: this wavefront's supported resamples
+    for (int32_t b0 = 0; b0 < nBoot; b0 += (int32_t) blockDim.x) {
+        const int32_t b = b0 + (int32_t) threadIdx.x;
+        const bool mine = b < nBoot;
+        double raw[6] = {0, 0, 0, 0, 0, 0};
+        // (rolled: one copy of the staging code, whose 20-state pieces need more registers than the walk)
+#pragma unroll 1
+        for (int j0 = 0; j0 < 6; j0 += P) {
+            if (j0 > 0 || b0 > 0) __syncthreads();   // every walk of the staged pairs is over
+#pragma unroll 1
+            for (int jj = 0; jj < P; jj++) {
+                // pair j of qAB, qAC, qAD, qBC, qBD, qCD: x = 0 0 0 1 1 2, y = 1 2 3 2 3 3
+                const int x = (0x211000 >> (4 * (j0 + jj))) & 15, y = (0x332321 >> (4 * (j0 + jj))) & 15;
+                const int64_t qx = x == 0 ? q[0] : x == 1 ? q[1] : q[2], qy = y == 1 ? q[1] : y == 2 ? q[2] : q[3];
+                for (int32_t p = (int32_t) threadIdx.x; p < nPos; p += (int32_t) blockDim.x) {
+                    Col<REAL, NC> c1, c2;
+                    vft_load_col_ml<REAL, NC>(A, qx, p, c1);
+                    vft_load_col_ml<REAL, NC>(A, qy, p, c2);
+                    const REAL ww = c1.w * c2.w;      // numeric_t product, NJ.tcc:624-629
+                    const double w = (double) ww;
+                    spLong[jj * nPos + p] = make_double2(w * vft_piece<REAL, NC>(A, c1, c2, nullptr), w);
+                }
+            }
+            __syncthreads();
+            if (mine) {
+                double totp[P], totw[P];
+#pragma unroll
+                for (int jj = 0; jj < P; jj++) totp[jj] = totw[jj] = 0;
+                const int32_t *src = colT + b;
+                // four samples at a time: the next four indices are on their way from memory while these four are gathered
+                // from LDS, and the gathers are all issued before the adds (the adds stay in sample order)
+                auto add4 = [&](int32_t s0, int32_t s1, int32_t s2, int32_t s3) {
+                    double2 v[P][4];
+#pragma unroll
+                    for (int jj = 0; jj < P; jj++) {
+                        v[jj][0] = spLong[jj * nPos + s0];
+                        v[jj][1] = spLong[jj * nPos + s1];
+                        v[jj][2] = spLong[jj * nPos + s2];
+                        v[jj][3] = spLong[jj * nPos + s3];
+                    }
+#pragma unroll
+                    for (int jj = 0; jj < P; jj++)
+#pragma unroll
+                        for (int e = 0; e < 4; e++) {
+                            totp[jj] += v[jj][e].x;
+                            totw[jj] += v[jj][e].y;
+                        }
+                };
+                int32_t i = 0, a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+                if (nPos >= 4) {
+                    a0 = src[0];
+                    a1 = src[(int64_t) nBoot];
+                    a2 = src[(int64_t) 2 * nBoot];
+                    a3 = src[(int64_t) 3 * nBoot];
+                }
+                for (; i + 8 <= nPos; i += 4) {
+                    const int32_t *nx = src + (int64_t) (i + 4) * nBoot;
+                    const int32_t n0 = nx[0], n1 = nx[(int64_t) nBoot], n2 = nx[(int64_t) 2 * nBoot], n3 = nx[(int64_t) 3 * nBoot];
+                    add4(a0, a1, a2, a3);
+                    a0 = n0;
+                    a1 = n1;
+                    a2 = n2;
+                    a3 = n3;
+                }
+                if (i + 4 <= nPos) {
+                    add4(a0, a1, a2, a3);
+                    i += 4;
+                }
+                for (; i < nPos; i++) {
+                    const int32_t col = src[(int64_t) i * nBoot];
+#pragma unroll
+                    for (int jj = 0; jj < P; jj++) {
+                        const double2 v = spLong[jj * nPos + col];
+                        totp[jj] += v.x;
+                        totw[jj] += v.y;
+                    }
+                }
+#pragma unroll
+                for (int jj = 0; jj < P; jj++) {
+                    const double r = totw[jj] > 0.01 ? totp[jj] / totw[jj] : 3.0;
+#pragma unroll
+                    for (int j = 0; j < 6; j++) raw[j] = (j == j0 + jj) ? r : raw[j];   // (no indexed registers)
+                }
+            }
+        }
+        const bool sup = mine && vft_support_decide(raw, k, scoredist, eps, nFlagged, flagged, flagCap);
+        nSupport += (unsigned int) __popcll(__ballot(sup));
+    }
+    if ((threadIdx.x & 63) == 0 && nSupport) atomicAdd(&counts[k], nSupport);
 }
