@@ -452,6 +452,17 @@ int vft_walk_dual_choice(vft_ctx *ctx, uint32_t ticket, int32_t *alt, int32_t *s
    that sends dual commands (the workgroups log-correct every step's distance for the comparison of a dual command behind it). */
 int vft_walk_scoredist(vft_ctx *ctx, int32_t scoredist);
 int vft_walk_collect(vft_ctx *ctx, uint32_t ticket, void *dist);
+/* The same three with the pairs' WEIGHTS next to their distances (`-pseudo`, host/PseudoDistances.h: correctedPairDistances needs
+   profileDist's denominator of every pair): vft_walk_submit_w sets a flag in the command (bit 22 of its header, "answer the weight too"),
+   and workgroup w then sends the pair's weight - (numeric_t) (denom > 0 ? denom : 0.01), for two leaves the number of common columns - exactly what vft_profile_distances returns as that pair's weight - as further
+   self-tagged result granules of the same slot (csrc/vft_kernels_walk.h).  A command without the flag is answered exactly as before.
+   weight[6] is numeric_t like dist[6].  q must not be NULL (averages alone have no weights).  A ticket of vft_walk_submit_w is collected
+   with vft_walk_collect_w and one of vft_walk_submit / vft_walk_submit_dual with vft_walk_collect: the other way round is
+   VFT_ERR_INVALID, nothing is waited for and the ticket stays collectable by its own call.  A weight granule that does not arrive ends in
+   the same bounded wait and VFT_ERR_TIMEOUT as a missing distance. */
+int vft_walk_submit_w(vft_ctx *ctx, int32_t n, const int64_t *out, const int64_t *a, const int64_t *b, const int64_t *q, uint32_t *ticket);
+int vft_walk_collect_w(vft_ctx *ctx, uint32_t ticket, void *dist, void *weight);
+int vft_walk_step_w(vft_ctx *ctx, int32_t n, const int64_t *out, const int64_t *a, const int64_t *b, const int64_t *q, void *dist, void *weight);
 /* tools builds (-DVFT_WALK_TIMING): clock ticks (100 MHz) workgroup 0 of the servers of this process spent per phase -
    [0] waiting for a command, [1] averages, [2] waiting for the other workgroups' averages, [3] the pair's columns, [4] the ordered
    sums, [5] the answer, [6] steps with distances, [7] averages; zeros in a production build */

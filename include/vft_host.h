@@ -124,6 +124,16 @@ typedef struct {
                                    tree and build the profiles.  Refused before anything reaches the device: vft_nj_run (it returns
                                    joins), intree with slow (the NNI and SPR stages of a -slow run are not built), with a vft_comm of
                                    more than one rank, with fewer than 4 unique sequences, and every tree vft_read_tree refuses. */
+    double pseudo_weight;       /* `-pseudo [W]` (Options::pseudoWeight, correctedPairDistances NJ.tcc:1460-1488; "recommended if the alignment
+                                   has sequences with little or no overlap"): 0 = off (the last member: a zero-initialised caller keeps
+                                   everything above); W > 0 = every triplet / quartet of the minimum-evolution stages - the NNIs, every SPR
+                                   chain step, updateBranchLengths - replaces its raw distances by
+                                   (dist * weight + prior * W) / (weight + W), prior = the quartet's weighted mean distance (3.0 when
+                                   its weights add up to no more than 0.01), before the log correction (vft_pseudo_distances below).
+                                   The NJ phase, the supports, the ML stage's own arithmetic and vft_nj_make_matrix do not read it; with
+                                   slow only the ME lengths do.  The SPR chains send no dual commands then (vft_nj_last_walk_dual
+                                   reports 0 / 0).  Refused before anything reaches the device: a negative or non-finite weight, and
+                                   W > 0 with a vft_comm of more than one rank (the lane exchange carries no weights). */
 } vft_nj_options;
 #define VFT_NJ_DEBUG_HOST_JOINS 1
 #define VFT_NJ_DEBUG_HOST_LISTS 2
@@ -238,6 +248,15 @@ int vft_nj_last_gamma(double *out);
    bytes written. */
 int vft_nj_make_matrix(vft_ctx *ctx, int64_t n_seqs, int32_t precision, const char *names, int32_t log_correct, int64_t slab_rows,
                        int32_t fd, const vft_comm *comm, double *seconds, int64_t *counts, char *err, int32_t err_len);
+
+/* correctedPairDistances behind profileDist (NJ.tcc:1460-1488; host/PseudoDistances.h), pure host code: the n_profiles * (n_profiles - 1) / 2
+   pairs of n_profiles = 3 (AB AC BC) or 4 (AB AC AD BC BD CD) profiles; dist / weight: numeric_t (precision 4 / 8 bytes) as
+   vft_profile_distances returns them; out: the pseudocount distances (pseudo_weight > 0; see vft_nj_options.pseudo_weight), log-corrected
+   (scoredist 0: Jukes-Cantor, else scoredist-like).  pseudo_weight == 0: the log-corrected distances alone.  The sum of dist * weight adds
+   numeric_t products (a float product in a float run), everything else is double.  VFT_ERR_INVALID: another n_profiles or precision, a NULL
+   pointer, a negative or non-finite pseudo_weight. */
+int vft_pseudo_distances(int32_t n_profiles, int32_t precision, const void *dist, const void *weight, double pseudo_weight, int32_t scoredist,
+                         double *out);
 
 /* The first n values of the random stream the bootstrap columns are drawn from (Knuth's ran_array at its default
    seed, as the reference uses it, Knuth.cpp:95-111): exported so that tests can pin the host generator. */

@@ -8,6 +8,7 @@ or - with -mllen - the tree of `VeryFastTree -nt -nome -mllen [-nocat | -cat N] 
     python tools/nj_tree.py in.fasta -full -lg -double > tree.nwk     # proteins: `VeryFastTree -lg -double-precision` (-aa / -jtt, -wag, -lg)
     python tools/nj_tree.py in.fasta -full -threads 64 [-gamma] [-spr N] > tree.nwk   # the schedule of `VeryFastTree -threads 64`; -gamma; -spr N rounds
     python tools/nj_tree.py in.fasta -intree start.nwk [-mllen ... | -full ...] > tree.nwk   # `VeryFastTree -intree start.nwk ...`: no NJ phase
+    python tools/nj_tree.py in.fasta [any mode above] -pseudo [W] > tree.nwk   # `VeryFastTree ... -pseudo [W]`: pseudocount distances
     python tools/nj_tree.py -makematrix [-rawdist] [-aa] [-double] in.fasta > matrix.txt   # `VeryFastTree [-nt] [-rawdist] [-double-precision] -makematrix`
 
 Neighbour joining with top hits on the device (veryfasttree_amd/host/NJDriver.h), the root, minimum-evolution branch
@@ -26,6 +27,9 @@ several times, every unique sequence at least once, binary apart from the root) 
 way `VeryFastTree [-nt] [-rawdist] [-double-precision] -makematrix in.fasta` prints it (one row per sequence: its name, then
 " %f" per sequence; proteins with -aa: BLOSUM45 distances).  Every sequence is kept (no uniquify); repeated names are an
 error; not together with any tree option.
+-pseudo [W]: the reference's `-pseudo [weight]`, "recommended if the alignment has sequences with little or no overlap": the
+minimum-evolution stages (NNIs, SPR moves, ME branch lengths) estimate the distances of every triplet / quartet with pseudocounts of
+weight W (1.0 when no number follows; any W >= 0, 0 = off).  Not read by the NJ phase, the supports, the ML stage and -makematrix.
 -boot N: N resamples instead of 1000 for the supports, local (default mode) and SH-like (-mllen, -full) alike, as the reference's
 -boot; -boot 0 is -nosupport.  Local supports take every alignment the NJ phase takes (10 240 columns).
 Sequence normalisation and uniquify follow Alignment.cpp:453-526 (U -> T, '.' -> '-', duplicates by sequence string in
@@ -83,6 +87,25 @@ def parse_boot(args, nj_len=False):
     return 0 if ("-nosupport" in args or nj_len) else n_boot
 
 
+def parse_pseudo(args):
+    """`-pseudo [W]`: the token behind -pseudo is the weight if it is a number (a negative or non-finite one is refused), else the weight
+    is 1.0 and the token is left alone; returns (weight or 0.0 without the option, args without the option)"""
+    if "-pseudo" not in args:
+        return 0.0, list(args)
+    args = list(args)
+    k = args.index("-pseudo")
+    weight, used = 1.0, 1
+    if k + 1 < len(args):
+        try:
+            weight, used = float(args[k + 1]), 2
+        except ValueError:
+            pass
+    if not (weight >= 0.0) or weight == float("inf"):
+        sys.exit("-pseudo takes a weight >= 0, not '%s'" % args[k + 1])
+    del args[k:k + used]
+    return weight, args
+
+
 MAKEMATRIX_FLAGS = ("-makematrix", "-rawdist", "-aa", "-double")
 
 
@@ -110,6 +133,7 @@ def main():
     args = sys.argv[1:]
     if "-makematrix" in args:
         return main_makematrix(args)
+    pseudo, args = parse_pseudo(args)
     if not args or args[0].startswith("-"):
         sys.exit(__doc__)
     fastest, double, nj_len = "-fastest" in args, "-double" in args, "-nj-lengths" in args
@@ -174,7 +198,7 @@ def main():
     try:
         tree, loglk = nj_newick(lambda n, L: HipProfileOps(n, L, 20 if aa else 4, dt, max_nodes=3 * n), codes_all, names, fastest=fastest,
                                 dtype=dt, me_lengths=not nj_len, unique=(np.array(unique_first, np.int64), aln_next),
-                                n_bootstrap=n_boot, mllen=mllen, return_loglk=True, slow=slow, intree=intree, **extra)
+                                n_bootstrap=n_boot, mllen=mllen, return_loglk=True, slow=slow, intree=intree, pseudo=pseudo, **extra)
     except VftError as e:
         if intree is None:
             raise

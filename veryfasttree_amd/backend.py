@@ -31,7 +31,7 @@ EXPORTS = [
     "vft_set_node_scalars", "vft_get_node_scalars", "vft_set_out_distances", "vft_get_out_distances", "vft_out_distance_mirror", "vft_set_max_node",
     "vft_profile_upload", "vft_profile_download", "vft_profile_nvectors", "vft_average_profiles", "vft_out_profile_full", "vft_out_profile_partial", "vft_out_profile_finish",
     "vft_out_profile_update", "vft_out_profile_upload", "vft_out_profile_download", "vft_out_distances", "vft_sweep",
-    "vft_sweep_batch", "vft_sweep_batch_view", "vft_set_shard", "vft_merge_hits", "vft_merge_hits_batch", "vft_sweep_info", "vft_sweep_batch_info", "vft_sweep_results", "vft_pair_distances", "vft_pair_loglk", "vft_posterior_profiles", "vft_set_profile_rows", "vft_average_chain", "vft_average_chains", "vft_profiles_differ", "vft_get_max_nodes", "vft_get_n_codes", "vft_walk_step", "vft_walk_server_start", "vft_walk_server_stop", "vft_walk_submit", "vft_walk_submit_dual", "vft_walk_dual_choice", "vft_walk_scoredist", "vft_walk_collect", "vft_walk_server_ticks", "vft_posterior_chains_blen", "vft_ml_quartet_nni_flags", "vft_branch_lengths_set", "vft_branch_lengths_get", "vft_branch_lengths_gather", "vft_branch_lengths_scatter", "vft_posterior_profiles_blen", "vft_posterior_chain_blen", "vft_ml_optimize_splits", "vft_ml_split_tests", "vft_ml_quartet_nni", "vft_ml_eval_count",
+    "vft_sweep_batch", "vft_sweep_batch_view", "vft_set_shard", "vft_merge_hits", "vft_merge_hits_batch", "vft_sweep_info", "vft_sweep_batch_info", "vft_sweep_results", "vft_pair_distances", "vft_pair_loglk", "vft_posterior_profiles", "vft_set_profile_rows", "vft_average_chain", "vft_average_chains", "vft_profiles_differ", "vft_get_max_nodes", "vft_get_n_codes", "vft_walk_step", "vft_walk_server_start", "vft_walk_server_stop", "vft_walk_submit", "vft_walk_submit_dual", "vft_walk_dual_choice", "vft_walk_scoredist", "vft_walk_collect", "vft_walk_submit_w", "vft_walk_collect_w", "vft_walk_step_w", "vft_walk_server_ticks", "vft_posterior_chains_blen", "vft_ml_quartet_nni_flags", "vft_branch_lengths_set", "vft_branch_lengths_get", "vft_branch_lengths_gather", "vft_branch_lengths_scatter", "vft_posterior_profiles_blen", "vft_posterior_chain_blen", "vft_ml_optimize_splits", "vft_ml_split_tests", "vft_ml_quartet_nni", "vft_ml_eval_count",
     "vft_join_nodes", "vft_profile_distances", "vft_split_supports", "vft_timer_start", "vft_timer_stop_ms", "vft_sweep_kernel_ms", "vft_sweep_table_kernel_ms", "vft_sweep_kernel_sweeps",
     "vft_debug_log", "vft_debug_option", "vft_tophits_create", "vft_tophits_upload", "vft_tophits_download", "vft_tophits_best", "vft_tophits_join", "vft_tophits_refresh", "vft_nj_engine_create", "vft_nj_engine_set_state", "vft_nj_engine_get_state", "vft_nj_engine_visible_set", "vft_nj_engine_visible_get", "vft_nj_engine_nodes_set", "vft_nj_engine_topvisible_set", "vft_nj_engine_topvisible_get", "vft_nj_engine_reset_candidates", "vft_nj_engine_enqueue", "vft_nj_engine_poll", "vft_nj_engine_resume", "vft_nj_engine_log", "vft_nj_engine_adopt", "vft_leaf_block_distances", "vft_set_shard_mode", "vft_join_fused", "vft_block_distances", "vft_pair_distances_refresh",
     "vft_exhaustive_create", "vft_exhaustive_destroy", "vft_exhaustive_fill", "vft_exhaustive_join", "vft_exhaustive_search", "vft_exhaustive_row",
@@ -60,7 +60,7 @@ class _NJOptions(C.Structure):
     _fields_ = [("fastest", I32), ("use_tophits_2nd", I32), ("tophits_mult", C.c_double), ("tophits_close", C.c_double),
                 ("tophits_refresh", C.c_double), ("topvisible_mult", C.c_double), ("stale_out_limit", C.c_double),
                 ("f_reset_out_profile", C.c_double), ("n_reset_out_profile", I32), ("tophits2_safety", I32),
-                ("tophits2_mult", C.c_double), ("tophits2_refresh", C.c_double), ("scoredist", I32), ("mllen", I32), ("me_nni", I32), ("ml_nni", I32), ("spr", I32), ("gtr", I32), ("aa_model", I32), ("comm", P), ("threads", I32), ("debug_flags", I32), ("gamma", I32), ("out_profile_parts", I32), ("slow", I32), ("intree", C.c_char_p)]
+                ("tophits2_mult", C.c_double), ("tophits2_refresh", C.c_double), ("scoredist", I32), ("mllen", I32), ("me_nni", I32), ("ml_nni", I32), ("spr", I32), ("gtr", I32), ("aa_model", I32), ("comm", P), ("threads", I32), ("debug_flags", I32), ("gamma", I32), ("out_profile_parts", I32), ("slow", I32), ("intree", C.c_char_p), ("pseudo_weight", C.c_double)]
 
 
 class _ExhaustiveBest(C.Structure):
@@ -255,9 +255,10 @@ def uniquify(codes):
 
 def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtype=np.float32, me_lengths=False,
               unique=None, scoredist=False, n_bootstrap=0, mllen=0, return_loglk=False, return_rates=False, me_nni=False, ml_nni=0, spr=0, gtr=False, return_gtr=False,
-              aa_model=None, comm=None, threads=1, debug_flags=0, gamma=False, out_profile_parts=0, slow=False, intree=None):
+              aa_model=None, comm=None, threads=1, debug_flags=0, gamma=False, out_profile_parts=0, slow=False, intree=None, pseudo=0.0):
     """The NJ phase of the whole alignment `codes_all` (duplicates included) as the reference's "NJ" tree string.
     intree (str): `-intree` - Newick text of a starting tree; the NJ phase does not run (vft_nj_options.intree).
+    pseudo (float): `-pseudo W` - pseudocount distances in the minimum-evolution stages, 0 = off (vft_nj_options.pseudo_weight).
     make_ops(n_unique, n_pos) -> HipProfileOps for the unique sequences (max_nodes >= 3 * n_unique with me_lengths:
     then the tree carries the minimum-evolution branch lengths, the final output of -noml -nome -nosupport)."""
     lib = load_host_library()
@@ -275,7 +276,7 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
     opt = _NJOptions(1 if fastest else 0, 1 if second_level else 0, 1.0, -1.0, 0.5 if fastest else 0.8, 1.5, 0.01, 0.02,
                      200, 3, 1.0, 0.6, 1 if scoredist else 0, int(mllen), 1 if me_nni else 0, int(ml_nni), int(spr), 1 if gtr else 0,
                      AA_MODELS[aa_model], comm.pointer() if comm is not None else None, int(threads), int(debug_flags), 1 if gamma else 0, int(out_profile_parts), 1 if slow else 0,
-                     None if intree is None else _intree_bytes(intree))
+                     None if intree is None else _intree_bytes(intree), float(pseudo))
     blob = b"".join(nm.encode() + b"\0" for nm in names)
     cap = 64 * len(names) + len(blob) + 1024
     out = C.create_string_buffer(cap)
@@ -300,6 +301,22 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
     if return_loglk:
         return out.value.decode(), loglk[:n_rounds.value]
     return out.value.decode()
+
+
+def pseudo_distances(dist, weight, pseudo, scoredist=False):
+    """correctedPairDistances behind profileDist (vft_pseudo_distances, host/PseudoDistances.h; no device): dist / weight = the 3 or 6
+    numeric_t pairs of a triplet / quartet (float32 or float64 arrays); returns the log-corrected pseudocount distances (float64)."""
+    lib = load_host_library()
+    dist = np.ascontiguousarray(dist)
+    weight = np.ascontiguousarray(weight, dist.dtype)
+    if dist.dtype not in (np.float32, np.float64) or dist.shape != weight.shape or dist.ndim != 1 or len(dist) not in (3, 6):
+        raise VftError("pseudo_distances: 3 or 6 float32 / float64 distances and as many weights")
+    out = np.zeros(len(dist), np.float64)
+    lib.vft_pseudo_distances.argtypes = [I32, I32, P, P, C.c_double, I32, P]
+    rc = lib.vft_pseudo_distances(3 if len(dist) == 3 else 4, dist.dtype.itemsize, _ptr(dist), _ptr(weight), float(pseudo), 1 if scoredist else 0, _ptr(out))
+    if rc != 0:
+        raise VftError("vft_pseudo_distances: bad arguments (a negative or non-finite weight?)")
+    return out
 
 
 def _intree_bytes(text):
@@ -394,6 +411,14 @@ def last_stage_seconds():
     lib.vft_nj_last_walk_dual(_ptr(dual))
     out.update(spr_dual_commands=int(dual[0]), spr_dual_continuations=int(dual[1]))
     return out
+
+
+def last_walk_dual():
+    """(dual commands sent, continuations the walk server ran on its own) in the SPR chains of the last nj_newick of this process
+    (vft_nj_last_walk_dual); 0 / 0 with pseudo > 0: no dual command is sent then"""
+    out = np.zeros(2, np.int64)
+    load_host_library().vft_nj_last_walk_dual(_ptr(out))
+    return int(out[0]), int(out[1])
 
 
 def last_lane_exchange():

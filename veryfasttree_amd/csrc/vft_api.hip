@@ -183,6 +183,7 @@ struct vft_ctx {
         bool disabled = false;  // VFT_DEBUG_NO_WALK_SERVER
         bool allocated = false; // every buffer of the server exists (set behind the last allocation of the first start)
         bool scoredist = false; // logCorrect's flavour of the walk (bit 21 of every command: the workgroups log-correct their distance for a dual command that may follow)
+        bool wantWeight[VFT_WS_RING] = {};   // slot seq % RING: the command in it asked for the pairs' weights too (vft_walk_submit_w)
     } ws;
     // the join loop on the device (vft_kernels_njengine.h)
     void *njState = nullptr, *njVisD = nullptr;
@@ -1378,19 +1379,25 @@ static inline void ws_put(vft_ctx *c, uint32_t seq, int g, uint32_t data) {
     volatile unsigned long long *slot = c->ws.hMail + (size_t) (seq % VFT_WS_RING) * VFT_WS_GRAN;
     slot[g] = ((unsigned long long) seq << 32) | (unsigned long long) data;
 }
-// all six workgroups have answered command `seq` (isDist: with a distance, copied to dist[6] when not null)
-static bool ws_answered(vft_ctx *c, uint32_t seq, bool wide) {
+// all six workgroups have answered command `seq` (wide: both halves of a double; weights: the weight granules of a
+// vft_walk_submit_w command as well - they are written behind the distance, so the distance alone does not tell)
+static bool ws_answered(vft_ctx *c, uint32_t seq, bool wide, bool weights = false) {
     const volatile unsigned long long *slot = c->ws.hRes + (size_t) (seq % VFT_WS_RING) * VFT_WS_RESG;
     for (int w = 0; w < VFT_WS_NWG; w++) {
         if ((uint32_t) (slot[2 * w] >> 32) != seq) return false;
         if (wide && (uint32_t) (slot[2 * w + 1] >> 32) != seq) return false;
     }
+    if (weights)
+        for (int w = 0; w < VFT_WS_NWG; w++) {
+            if ((uint32_t) (slot[VFT_WS_RES_WEIGHT + 2 * w] >> 32) != seq) return false;
+            if (wide && (uint32_t) (slot[VFT_WS_RES_WEIGHT + 2 * w + 1] >> 32) != seq) return false;
+        }
     return true;
 }
-static int ws_wait(vft_ctx *c, uint32_t seq, bool wide) {
+static int ws_wait(vft_ctx *c, uint32_t seq, bool wide, bool weights = false) {
     std::chrono::steady_clock::time_point t0;
     for (long spins = 0;; spins++) {
-        if (ws_answered(c, seq, wide)) {
+        if (ws_answered(c, seq, wide, weights)) {
             if ((int32_t) (seq - c->ws.acked) > 0) c->ws.acked = seq;   // (the workgroups answer in order)
             return VFT_OK;
         }
@@ -1398,7 +1405,7 @@ static int ws_wait(vft_ctx *c, uint32_t seq, bool wide) {
         if (spins >= 200000 && (spins & 0xFFFF) == 0) {
             const hipError_t e = hipStreamQuery(c->ws.stream);
             if (e == hipSuccess) {   // the server has left
-                if (ws_answered(c, seq, wide)) continue;
+                if (ws_answered(c, seq, wide, weights)) continue;
                 c->ws.up = false;
                 if (g_walkServerOwner == c) g_walkServerOwner = nullptr;
                 return fail(c, VFT_ERR_TIMEOUT, "the walk server has stopped (status %llu %llu %llu %llu %llu %llu) with command %u unanswered",
@@ -1411,7 +1418,8 @@ static int ws_wait(vft_ctx *c, uint32_t seq, bool wide) {
     }
 }
 // one command: nOps averages (<= VFT_WS_MAXOPS) and, with q, the six distances of the quartet; returns its sequence number
-static int ws_command(vft_ctx *c, int32_t nOps, const int64_t *out, const int64_t *a, const int64_t *b, const int64_t *q, uint32_t *seqOut) {
+// (weights: with q, the six weights as well - bit VFT_WS_WEIGHT_BIT)
+static int ws_command(vft_ctx *c, int32_t nOps, const int64_t *out, const int64_t *a, const int64_t *b, const int64_t *q, uint32_t *seqOut, bool weights = false) {
     const uint32_t seq = ++c->ws.seq;
     const bool wide = c->rs == 8;
     // the slot of seq is the slot of seq - RING, and the answers share a ring of the same length: stay well inside it
@@ -1424,7 +1432,9 @@ static int ws_command(vft_ctx *c, int32_t nOps, const int64_t *out, const int64_
         ws_put(c, seq, 6 + 3 * k, (uint32_t) (int32_t) a[k]);
         ws_put(c, seq, 7 + 3 * k, (uint32_t) (int32_t) b[k]);
     }
-    ws_put(c, seq, 0, VFT_WS_CMD_WORK | ((uint32_t) nOps << 8) | (q ? 1u << 16 : 0u) | (noWait ? 1u << 17 : 0u) | (c->ws.scoredist ? 1u << 21 : 0u));
+    c->ws.wantWeight[seq % VFT_WS_RING] = q && weights;
+    ws_put(c, seq, 0, VFT_WS_CMD_WORK | ((uint32_t) nOps << 8) | (q ? 1u << 16 : 0u) | (noWait ? 1u << 17 : 0u) | (c->ws.scoredist ? 1u << 21 : 0u) |
+                      (q && weights ? 1u << VFT_WS_WEIGHT_BIT : 0u));
     if (c->ws.mailOnDevice) __builtin_ia32_sfence();
     *seqOut = seq;
     return VFT_OK;
@@ -1529,20 +1539,27 @@ static int walk_ids_ok(vft_ctx *c, int32_t n, const int64_t *out, const int64_t 
 
 // a step (or, with q == NULL, averages alone) handed to the server; *ticket answers vft_walk_collect.  Steps with more than
 // VFT_WS_MAXOPS averages go down as several commands, the distances with the last.
-extern "C" int vft_walk_submit(vft_ctx *c, int32_t n, const int64_t *out, const int64_t *a, const int64_t *b, const int64_t *q, uint32_t *ticket) {
-    if (!c || n < 0 || (n > 0 && (!out || !a || !b)) || !ticket) return VFT_ERR_INVALID;
-    if (!c->ws.up) return fail(c, VFT_ERR_STATE, "vft_walk_submit: the walk server is not running (vft_walk_server_start)");
-    if (int r = walk_ids_ok(c, n, out, a, b, q, "vft_walk_submit")) return r;
+static int walk_submit(vft_ctx *c, int32_t n, const int64_t *out, const int64_t *a, const int64_t *b, const int64_t *q, uint32_t *ticket, bool weights, const char *who) {
+    if (!c || n < 0 || (n > 0 && (!out || !a || !b)) || !ticket || (weights && !q)) return VFT_ERR_INVALID;
+    if (!c->ws.up) return fail(c, VFT_ERR_STATE, "%s: the walk server is not running (vft_walk_server_start)", who);
+    if (int r = walk_ids_ok(c, n, out, a, b, q, who)) return r;
     int32_t first = 0;
     uint32_t seq = 0;
     do {
         const int32_t m = n - first > VFT_WS_MAXOPS ? VFT_WS_MAXOPS : n - first;
         const bool last = first + m == n;
-        if (int r = ws_command(c, m, out + first, a + first, b + first, last ? q : nullptr, &seq)) return r;
+        if (int r = ws_command(c, m, out + first, a + first, b + first, last ? q : nullptr, &seq, weights)) return r;
         first += m;
     } while (first < n);
     *ticket = seq;
     return VFT_OK;
+}
+extern "C" int vft_walk_submit(vft_ctx *c, int32_t n, const int64_t *out, const int64_t *a, const int64_t *b, const int64_t *q, uint32_t *ticket) {
+    return walk_submit(c, n, out, a, b, q, ticket, false, "vft_walk_submit");
+}
+// ... and the six weights next to the six distances (bit VFT_WS_WEIGHT_BIT of the command that carries the quartet); collected by vft_walk_collect_w
+extern "C" int vft_walk_submit_w(vft_ctx *c, int32_t n, const int64_t *out, const int64_t *a, const int64_t *b, const int64_t *q, uint32_t *ticket) {
+    return walk_submit(c, n, out, a, b, q, ticket, true, "vft_walk_submit_w");
 }
 // Both continuations of an SPR chain behind the step that is running (vft_kernels_walk.h "DUAL command"): alternative 0 is taken when the
 // comparison of the PREVIOUS command's distances says "swap B and C" (criteria[1] < criteria[2]), alternative 1 otherwise.  q0 / q1 == NULL:
@@ -1564,6 +1581,7 @@ extern "C" int vft_walk_submit_dual(vft_ctx *c, int32_t n0, const int64_t *out0,
     const uint32_t seq = ++c->ws.seq;
     while ((int32_t) (seq - c->ws.acked) > VFT_WS_RING / 2)
         if (int r = ws_wait(c, c->ws.acked + 1, false)) return r;
+    c->ws.wantWeight[seq % VFT_WS_RING] = false;
     int g = 1;
     for (int t = 0; t < 4; t++) ws_put(c, seq, g++, q0 ? (uint32_t) (int32_t) q0[t] : 0u);
     for (int32_t k = 0; k < n0; k++) {
@@ -1607,16 +1625,31 @@ extern "C" int vft_walk_dual_choice(vft_ctx *c, uint32_t ticket, int32_t *alt, i
 }
 
 // waits for the answer to a ticket; dist[6] (numeric_t) when the step asked for distances (NULL: an acknowledgement is waited for)
-extern "C" int vft_walk_collect(vft_ctx *c, uint32_t ticket, void *dist) {
-    if (!c) return VFT_ERR_INVALID;
+static int walk_collect(vft_ctx *c, uint32_t ticket, void *dist, void *weight, const char *who) {
     const bool wide = c->rs == 8 && dist != nullptr;
     // The answers share a ring of VFT_WS_RING slots: a ticket that old has had its slot rewritten (ws_command's flow control runs the
     // sequence numbers at most VFT_WS_RING / 2 ahead of the acknowledged ones, not of the tickets a caller still holds) - say so at
     // once instead of spinning for a tag that will never show again.
     if ((int32_t) (c->ws.seq - ticket) >= VFT_WS_RING)
-        return fail(c, VFT_ERR_STATE, "vft_walk_collect: ticket %u is %d commands old, its answer slot has been reused (collect within %d submissions)",
-                    ticket, (int) (c->ws.seq - ticket), VFT_WS_RING - 1);
-    if (int r = ws_wait(c, ticket, wide)) return r;
+        return fail(c, VFT_ERR_STATE, "%s: ticket %u is %d commands old, its answer slot has been reused (collect within %d submissions)",
+                    who, ticket, (int) (c->ws.seq - ticket), VFT_WS_RING - 1);
+    // (the slot's flag is this ticket's: a later command in the same slot would have made the ticket too old above)
+    if ((int32_t) (c->ws.seq - ticket) >= 0 && c->ws.wantWeight[ticket % VFT_WS_RING] != (weight != nullptr))
+        return fail(c, VFT_ERR_INVALID, "%s: ticket %u was submitted %s the weights (vft_walk_submit_w goes with vft_walk_collect_w, vft_walk_submit with vft_walk_collect)",
+                    who, ticket, weight ? "without" : "with");
+    if (int r = ws_wait(c, ticket, wide, weight != nullptr)) return r;
+    if (weight) {
+        const volatile unsigned long long *slot = c->ws.hRes + (size_t) (ticket % VFT_WS_RING) * VFT_WS_RESG + VFT_WS_RES_WEIGHT;
+        for (int w = 0; w < VFT_WS_NWG; w++) {
+            if (c->rs == 4) {
+                const uint32_t v = (uint32_t) slot[2 * w];
+                memcpy((char *) weight + 4 * w, &v, 4);
+            } else {
+                const unsigned long long v = (slot[2 * w] & 0xFFFFFFFFull) | (slot[2 * w + 1] << 32);
+                memcpy((char *) weight + 8 * w, &v, 8);
+            }
+        }
+    }
     if (dist) {
         const volatile unsigned long long *slot = c->ws.hRes + (size_t) (ticket % VFT_WS_RING) * VFT_WS_RESG;
         for (int w = 0; w < VFT_WS_NWG; w++) {
@@ -1630,6 +1663,14 @@ extern "C" int vft_walk_collect(vft_ctx *c, uint32_t ticket, void *dist) {
         }
     }
     return VFT_OK;
+}
+extern "C" int vft_walk_collect(vft_ctx *c, uint32_t ticket, void *dist) {
+    if (!c) return VFT_ERR_INVALID;
+    return walk_collect(c, ticket, dist, nullptr, "vft_walk_collect");
+}
+extern "C" int vft_walk_collect_w(vft_ctx *c, uint32_t ticket, void *dist, void *weight) {
+    if (!c || !dist || !weight) return VFT_ERR_INVALID;
+    return walk_collect(c, ticket, dist, weight, "vft_walk_collect_w");
 }
 static int walk_ids_ok(vft_ctx *c, int32_t n, const int64_t *out, const int64_t *a, const int64_t *b, const int64_t *q, const char *who) {
     for (int32_t k = 0; k < n; k++) {
@@ -1648,6 +1689,13 @@ extern "C" int vft_walk_step(vft_ctx *c, int32_t n, const int64_t *out, const in
     uint32_t ticket;
     if (int r = vft_walk_submit(c, n, out, a, b, q, &ticket)) return r;
     return vft_walk_collect(c, ticket, dist);
+}
+extern "C" int vft_walk_step_w(vft_ctx *c, int32_t n, const int64_t *out, const int64_t *a, const int64_t *b, const int64_t *q, void *dist, void *weight) {
+    if (!c || n < 0 || (n > 0 && (!out || !a || !b)) || !q || !dist || !weight) return VFT_ERR_INVALID;
+    if (!c->ws.up) return fail(c, VFT_ERR_STATE, "vft_walk_step_w: the walk server is not running (vft_walk_server_start); the caller makes the two plain calls");
+    uint32_t ticket;
+    if (int r = vft_walk_submit_w(c, n, out, a, b, q, &ticket)) return r;
+    return vft_walk_collect_w(c, ticket, dist, weight);
 }
 
 // differ[k] = 1 when the profiles of nodes a[k] and b[k] (rows or tile streams, internal or leaf) are not bit-identical.  Waits.

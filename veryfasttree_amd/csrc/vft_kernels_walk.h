@@ -33,7 +33,8 @@
 #define VFT_WS_GRAN 64       // granules per command slot (one per lane of the polling wavefront)
 #define VFT_WS_RING 16       // command slots
 #define VFT_WS_MAXOPS 19     // averages per command: 5 + 3 * 19 = 62 granules
-#define VFT_WS_RESG 16       // result granules per slot: workgroup w writes [2 w] (and [2 w + 1]: the high half of a double)
+#define VFT_WS_RESG 32       // result granules per slot: workgroup w writes [2 w] (and [2 w + 1]: the high half of a double); [12] a dual command's
+                             // choice; [16 + 2 w] (and [16 + 2 w + 1]) the pair's weight when the command asks for it (VFT_WS_WEIGHT_BIT)
 #define VFT_WS_CMD_WORK 1u
 #define VFT_WS_CMD_STOP 2u
 // A DUAL command (round 6) carries BOTH continuations of an SPR chain: which NNI follows step k is one comparison of step k's own
@@ -47,6 +48,13 @@
 // Granules: [0] header, [1..4] quartet 0, [5 .. 5 + 3 n0) averages 0, then quartet 1 (4) and averages 1 (3 n1): n0 + n1 <= 18.
 #define VFT_WS_DUAL_BIT 18
 #define VFT_WS_DUAL_MAXOPS 18
+// Bit 22 of a plain command's header (`-pseudo`: correctedPairDistances, NJ.tcc:1460-1488, needs profileDist's denominator of every pair):
+// "answer the weight too" - workgroup w sends its pair's weight - (REAL) (denom > 0 ? denom : 0.01), for two leaves (REAL) denom -, exactly what vft_profile_distances returns as the pair's weight, as one or two
+// further self-tagged granules of the same slot, right behind its distance.  A command without the bit is answered as ever: the same
+// granules at the same indices, nothing else stored or waited for.  Dual commands never carry it (the comparison on the device works on
+// log-corrected distances without pseudocounts: the host sends no dual commands while it wants weights).
+#define VFT_WS_WEIGHT_BIT 22
+#define VFT_WS_RES_WEIGHT 16   // first weight granule of a result slot
 #define VFT_WS_RES_CHOICE 12   // result granule of a dual command: {seq, 1 | alternative << 1 | not-a-device-step << 2} (workgroup 0)
 #define VFT_WS_FLAG_DIST 16    // flags[16 + 16 * (seq & 1) + 2 w (+ 1)]: workgroup w's LOG-CORRECTED distance of command seq (a double), tagged low / high half
 #define VFT_WS_SC1 16        // aux bits of the buffer intrinsics on gfx950: write-through stores / L1-bypassing loads
@@ -502,6 +510,18 @@ __global__ __launch_bounds__(VFT_WS_WG_OF(NC)) void k_walk_server(Arena<REAL> A,
             } else {
                 __hip_atomic_store(out, ((unsigned long long) seq << 32) | (unsigned long long) (unsigned) __double2loint(d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 __hip_atomic_store(out + 1, ((unsigned long long) seq << 32) | (unsigned long long) (unsigned) __double2hiint(d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+            if ((hdr >> VFT_WS_WEIGHT_BIT) & 1u) {   // ... and the pair's weight (the host waits for these granules too, by their own tags)
+                // two leaves (ids below nSeqs; the command is still in sCmd): the plain call answers seqDist's weight, the column count, 0 for none in common
+                const bool leafPair = (int32_t) sCmd[1 + pi] < (int32_t) A.d.nSeqs && (int32_t) sCmd[1 + pj] < (int32_t) A.d.nSeqs;
+                const REAL wt = (REAL) (leafPair || denom > 0 ? denom : 0.01);   // as vft_pair_block: profileDist's weight (NJ.tcc:1187), seqDist's for two leaves (:1618)
+                unsigned long long *wout = out + VFT_WS_RES_WEIGHT;
+                if constexpr (sizeof(REAL) == 4) {
+                    __hip_atomic_store(wout, ((unsigned long long) seq << 32) | (unsigned long long) __float_as_uint(wt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                } else {
+                    __hip_atomic_store(wout, ((unsigned long long) seq << 32) | (unsigned long long) (unsigned) __double2loint(wt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    __hip_atomic_store(wout + 1, ((unsigned long long) seq << 32) | (unsigned long long) (unsigned) __double2hiint(wt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
             }
         }
         if (threadIdx.x == 0) {

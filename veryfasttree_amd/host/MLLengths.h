@@ -26,6 +26,7 @@
 #include "../../include/vft_hip.h"
 #include "../../include/vft_host.h"
 #include "GtrModel.h"
+#include "PseudoDistances.h"
 
 namespace veryfasttree {
 
@@ -842,6 +843,7 @@ namespace veryfasttree {
                         std::copy(b, b + 6, pj.begin() + (long) (6 * t));
                     }
                     if (sharded()) {   /* six distances per quartet: this rank's share computed, all shares gathered */
+                        if (pseudoWeight > 0) throw std::invalid_argument("MLLengths: the lane exchange carries six distances per quartet and no weights (-pseudo with several ranks is refused)");
                         size_t per, m0, m1;
                         shareOf(K, per, m0, m1);
                         if (m1 > m0) chk(vft_profile_distances(ctx, (int64_t) (6 * (m1 - m0)), pi.data() + 6 * m0, pj.data() + 6 * m0, d.data() + 6 * m0, w.data() + 6 * m0));
@@ -865,7 +867,7 @@ namespace veryfasttree {
                         if (res[t].star) nStarTests++;
                     } else {
                         double c[6];
-                        for (int i = 0; i < 6; i++) c[i] = logCorrect((double) d[6 * t + (size_t) i], prm.scoredist);
+                        pseudoDistancesOfDevice<REAL>(6, d.data() + 6 * t, w.data() + 6 * t, pseudoWeight, prm.scoredist, c);
                         criteria[0] = c[0] + c[5];
                         criteria[1] = c[1] + c[4];
                         criteria[2] = c[2] + c[3];
@@ -1447,6 +1449,8 @@ namespace veryfasttree {
         int64_t nStarTests = 0;
         bool walkStepFused = true;   /* meSubmit: averages + distances as one step of the walk server (false: the two plain calls) */
         int64_t walkDualSent = 0, walkDualTaken = 0;   /* statistics: dual commands sent / continuations the walk server ran on its own */
+        double pseudoWeight = 0.0;   /* `-pseudo W`: the minimum-evolution criteria from pseudocount distances (host/PseudoDistances.h); the steps of the
+                                        walks then ask the walk server for the pairs' weights too (vft_walk_submit_w), and no dual command is sent */
         bool walkDual = true;        /* SPR chains hand both continuations of a step to the walk server (specContinuations); false: every step waits
                                         for the host's verdict (vft_nj_options.debug_flags & VFT_NJ_DEBUG_NO_WALK_DUAL) */
         bool walkServer = true;      /* the walks' steps go to resident workgroups through a mailbox (vft_walk_server_start); false: the
@@ -1785,6 +1789,7 @@ namespace veryfasttree {
             bool keyed = false;     /* key = the value numbers of the quartet's rows: the distances go to the memo table */
             uint64_t key[4];
             REAL d[6];
+            REAL w[6] = {0, 0, 0, 0, 0, 0};   /* the pairs' weights (profileDist's denominators): filled and read with pseudoWeight > 0 only */
         };
         /* ---- Both continuations of a chain step (round 6; csrc/vft_kernels_walk.h "DUAL command").  Step k of a chain (k >= 1) is on
            the device; which NNI it leads to - swap B and C, or A and C (findSPRSteps, NJ.tcc:1805-1859) - is one comparison of its own
@@ -1869,6 +1874,7 @@ namespace veryfasttree {
                 const MemoEntry &m = memoTable[(size_t) (vnHash(vnHash(t.key[0], t.key[1]), vnHash(t.key[2], t.key[3])) & (memoTable.size() - 1))];
                 if (m.used && m.q[0] == t.key[0] && m.q[1] == t.key[1] && m.q[2] == t.key[2] && m.q[3] == t.key[3]) {
                     for (int i = 0; i < 6; i++) t.d[i] = m.d[i];
+                    for (int i = 0; i < 6; i++) t.w[i] = m.w[i];
                     t.keyed = false;
                     stepsMemoised++;
                     return false;
@@ -1883,7 +1889,8 @@ namespace veryfasttree {
             if (!meBuild(node, upHave, q, t, q4, false)) return;
             const int64_t idD = q4[3];
             if (serverUp) {
-                chk(vft_walk_submit(ctx, (int32_t) qOut.size(), qOut.data(), qA.data(), qB.data(), q4, &t.ticket));
+                if (pseudoWeight > 0) chk(vft_walk_submit_w(ctx, (int32_t) qOut.size(), qOut.data(), qA.data(), qB.data(), q4, &t.ticket));
+                else chk(vft_walk_submit(ctx, (int32_t) qOut.size(), qOut.data(), qA.data(), qB.data(), q4, &t.ticket));
                 qOut.clear();
                 qA.clear();
                 qB.clear();
@@ -1891,11 +1898,11 @@ namespace veryfasttree {
                 return;
             }
             const int64_t pi[6] = {q[0], q[0], q[0], q[1], q[1], q[2]}, pj[6] = {q[1], q[2], idD, q[2], idD, idD};
-            REAL w[6];
             /* the queued averages and the six distances as one launch (vft_walk_step) while every profile is a plain row */
             bool fused = false;
             if (walkStepFused) {
-                const int rc = vft_walk_step(ctx, (int32_t) qOut.size(), qOut.data(), qA.data(), qB.data(), q4, t.d);
+                const int rc = pseudoWeight > 0 ? vft_walk_step_w(ctx, (int32_t) qOut.size(), qOut.data(), qA.data(), qB.data(), q4, t.d, t.w)
+                                                : vft_walk_step(ctx, (int32_t) qOut.size(), qOut.data(), qA.data(), qB.data(), q4, t.d);
                 if (rc == VFT_OK) {
                     fused = true;
                     qOut.clear();
@@ -1909,29 +1916,31 @@ namespace veryfasttree {
             }
             if (!fused) {
                 flushAverages();
-                chk(vft_profile_distances(ctx, 6, pi, pj, t.d, w));
+                chk(vft_profile_distances(ctx, 6, pi, pj, t.d, t.w));
             }
         }
         void meCollect(MeTicket &t, bool scoredist, double criteria[3]) {
             if (t.pending) {
+                const bool withWeights = pseudoWeight > 0;   /* (submitted with vft_walk_submit_w: meSubmit) */
                 if (walkStats) {
                     const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-                    chk(vft_walk_collect(ctx, t.ticket, t.d));
+                    chk(withWeights ? vft_walk_collect_w(ctx, t.ticket, t.d, t.w) : vft_walk_collect(ctx, t.ticket, t.d));
                     walkWaitSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                     walkDeviceSteps++;
                 } else
-                chk(vft_walk_collect(ctx, t.ticket, t.d));
+                chk(withWeights ? vft_walk_collect_w(ctx, t.ticket, t.d, t.w) : vft_walk_collect(ctx, t.ticket, t.d));
                 t.pending = false;
             }
             if (t.keyed) {
                 MemoEntry &m = memoTable[(size_t) (vnHash(vnHash(t.key[0], t.key[1]), vnHash(t.key[2], t.key[3])) & (memoTable.size() - 1))];
                 for (int i = 0; i < 4; i++) m.q[i] = t.key[i];
                 for (int i = 0; i < 6; i++) m.d[i] = t.d[i];
+                for (int i = 0; i < 6; i++) m.w[i] = t.w[i];
                 m.used = true;
                 t.keyed = false;
             }
             double c[6];
-            for (int i = 0; i < 6; i++) c[i] = logCorrect((double) t.d[i], scoredist);
+            pseudoDistancesOfDevice<REAL>(6, t.d, t.w, pseudoWeight, scoredist, c);
             criteria[0] = c[0] + c[5];
             criteria[1] = c[1] + c[4];
             criteria[2] = c[2] + c[3];
@@ -2139,6 +2148,7 @@ namespace veryfasttree {
         struct MemoEntry {
             uint64_t q[4];
             REAL d[6];
+            REAL w[6];
             bool used;
         };
         std::vector<uint64_t> rowVer;
@@ -2166,7 +2176,7 @@ namespace veryfasttree {
                 rowVer.assign(nIds, 0);
                 rowVerEpoch.assign(nIds, 0);
                 vnTable.assign((size_t) 1 << 16, VnEntry{0, 0, 0});
-                memoTable.assign((size_t) 1 << 15, MemoEntry{{0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}, false});
+                memoTable.assign((size_t) 1 << 15, MemoEntry{{0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0}, false});
                 vnEpoch = 0;
             }
             if (++vnEpoch == 0) {

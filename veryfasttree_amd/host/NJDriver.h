@@ -38,6 +38,7 @@
 
 #include "../../include/vft_host.h"
 #include "MLLengths.h"
+#include "PseudoDistances.h"
 #include "KnuthRng.h"
 #include "AAModels.h"
 
@@ -70,6 +71,10 @@ namespace veryfasttree {
         int seedBatch = 8;         /* setAllLeafTopHits: sweeps of this many unvisited seeds per device call (vft_sweep_batch); 1: a call per seed */
         bool walkServer = true;    /* refinement walks through the resident walk server (vft_walk_server_start); false: a launch per step */
         bool walkDual = true;      /* SPR chains hand both continuations of a step to the walk server (MLLengths::specContinuations); false: every step waits for the host's verdict */
+        /* `-pseudo W` (Options::pseudoWeight; host/PseudoDistances.h): every triplet / quartet of the minimum-evolution stages - NNIs, SPR chains,
+           updateBranchLengths - pulls its distances towards their weighted mean with this weight; 0 = off.  No dual commands then (the
+           workgroups would compare distances without pseudocounts). */
+        double pseudoWeight = 0.0;
         /* > 1: the refinement stages follow the reference's `-threads T` schedule (MLLengths.h "the subtree schedule") */
         int threads = 1;
         bool gamma = false;          /* `-gamma`: rescale the final lengths to a fitted discrete Gamma (MLLengths::branchlengthScale) */
@@ -688,7 +693,8 @@ namespace veryfasttree {
         /* updateBranchLengths (NJ.tcc:6514-6595) on the finished NJ topology, as the pipeline does before it prints a
            minimum-evolution tree (VeryFastTreeImpl.tcc:205-213): every branch length from log-corrected profile
            distances between the node's children / sibling / up-profile (correctedPairDistances NJ.tcc:1460-1488,
-           logCorrect :322-330; -nj weighting, no pseudocounts: the defaults).  The up-profile of an internal node X
+           logCorrect :322-330; -nj weighting; the pseudocounts of `-pseudo`
+           when opt.pseudoWeight > 0, from the weights the same call returns - host/PseudoDistances.h).  The up-profile of an internal node X
            (getUpProfile :3382-3434, useML = false) is average(sibling(X), up(parent X)), or the average of the two
            other children of the root; it lives on the device as node X + nSeqs, so the context must have been created
            with max_nodes >= 3 * nSeqs.  Up-profiles go level by level (one vft_average_profiles per depth), all
@@ -751,22 +757,15 @@ namespace veryfasttree {
                 chkT("vft_profile_distances", [&]() { return vft_profile_distances(ctx, cnt, pi.data() + p0, pj.data() + p0, pd.data() + p0, pw.data() + p0); });
             }
             /* 3. branch lengths (double arithmetic, stored as numeric_t) */
-            auto logCorrect = [&](double dist) {   /* NJ.tcc:322-330 */
-                const double maxscore = 3.0;
-                if (!opt.scoredist) dist = dist < 0.74 ? -0.75 * std::log(1.0 - dist * 4.0 / 3.0) : maxscore;   /* Jukes-Cantor */
-                else dist = dist < 0.99 ? -1.3 * std::log(1.0 - dist) : maxscore;                              /* scoredist-like */
-                return dist < maxscore ? dist : maxscore;
-            };
             for (int64_t v = 0; v < maxnode; v++) {
                 if (v == root) continue;
                 const int64_t f = firstPair[(size_t) v];
+                double d[6];
                 if (v < nSeqs) {
-                    const double dAB = logCorrect((double) pd[(size_t) f]), dAC = logCorrect((double) pd[(size_t) f + 1]),
-                                 dBC = logCorrect((double) pd[(size_t) f + 2]);
-                    branchlength[(size_t) v] = (REAL) ((dAB + dAC - dBC) / 2.0);
+                    pseudoDistancesOfDevice<REAL>(3, pd.data() + f, pw.data() + f, opt.pseudoWeight, opt.scoredist, d);   /* AB AC BC */
+                    branchlength[(size_t) v] = (REAL) ((d[0] + d[1] - d[2]) / 2.0);
                 } else {
-                    double d[6];
-                    for (int k = 0; k < 6; k++) d[k] = logCorrect((double) pd[(size_t) f + k]);
+                    pseudoDistancesOfDevice<REAL>(6, pd.data() + f, pw.data() + f, opt.pseudoWeight, opt.scoredist, d);
                     /* qAB 0, qAC 1, qAD 2, qBC 3, qBD 4, qCD 5 */
                     branchlength[(size_t) v] = (REAL) ((d[1] + d[2] + d[3] + d[4]) / 4.0 - (d[0] + d[5]) / 2.0);
                 }
@@ -814,7 +813,8 @@ namespace veryfasttree {
             treeArrays(par, ch);
             MLLengths<REAL> tree(ctx, nSeqs, maxnode, par.data(), ch.data(), root);
             tree.walkServer = opt.walkServer;
-            tree.walkDual = opt.walkDual;
+            tree.walkDual = opt.walkDual && !(opt.pseudoWeight > 0);
+            tree.pseudoWeight = opt.pseudoWeight;
             tree.comm = opt.comm;
             typename MLLengths<REAL>::NNIParams prm;
             prm.useML = false;

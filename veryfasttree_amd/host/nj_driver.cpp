@@ -194,6 +194,7 @@ static veryfasttree::NJOptions toOptions(const vft_nj_options *o) {
         opt.gamma = o->gamma != 0;
         opt.outProfileParts = o->out_profile_parts >= 2 ? o->out_profile_parts : 0;
         opt.slow = o->slow != 0;
+        opt.pseudoWeight = o->pseudo_weight;
         if (o->debug_flags & VFT_NJ_DEBUG_HOST_JOINS) opt.deviceJoins = false;
         if (o->debug_flags & VFT_NJ_DEBUG_HOST_LISTS) opt.deviceLists = false;
         if (o->debug_flags & VFT_NJ_DEBUG_HOST_RESET) opt.deviceReset = false;
@@ -282,6 +283,25 @@ static void checkSlow(const vft_nj_options *o) {
     if (o->comm && o->comm->world > 1) throw std::invalid_argument("-slow with a vft_comm of more than one rank is not built");
 }
 
+/* `-pseudo`: what is not built is refused before anything reaches the device (include/vft_host.h, vft_nj_options.pseudo_weight) */
+static void checkPseudo(const vft_nj_options *o) {
+    if (!o || o->pseudo_weight == 0) return;
+    if (!(o->pseudo_weight > 0) || !std::isfinite(o->pseudo_weight)) throw std::invalid_argument("-pseudo takes a finite weight >= 0");
+    if (o->comm && o->comm->world > 1)
+        throw std::invalid_argument("-pseudo with a vft_comm of more than one rank is not built: the lane exchange of the subtree schedule carries "
+                                    "six distances per quartet and no weights");
+}
+
+extern "C" int vft_pseudo_distances(int32_t nProfiles, int32_t precision, const void *dist, const void *weight, double pseudoWeight, int32_t scoredist,
+                                    double *out) {
+    if ((nProfiles != 3 && nProfiles != 4) || (precision != 4 && precision != 8) || !dist || !weight || !out) return VFT_ERR_INVALID;
+    if (!(pseudoWeight >= 0) || !std::isfinite(pseudoWeight)) return VFT_ERR_INVALID;
+    const int nPairs = nProfiles * (nProfiles - 1) / 2;
+    if (precision == 8) veryfasttree::pseudoDistances<double>(nPairs, (const double *) dist, (const double *) weight, pseudoWeight, scoredist != 0, out);
+    else veryfasttree::pseudoDistances<float>(nPairs, (const float *) dist, (const float *) weight, pseudoWeight, scoredist != 0, out);
+    return VFT_OK;
+}
+
 template<typename REAL>
 static std::string runTree(vft_ctx *ctx, const uint8_t *codes, int64_t nSeqs, int64_t nPos, const vft_nj_options *o,
                            bool meLengths, int32_t nBootstrap, const int64_t *uniqueFirst, const int64_t *alnNext,
@@ -356,6 +376,7 @@ extern "C" int vft_nj_ml_newick(vft_ctx *ctx, const uint8_t *codes, int64_t nSeq
     try {
         checkIntree(opt, nSeqs);
         checkSlow(opt);
+        checkPseudo(opt);
         std::vector<double> ll, rates;
         std::vector<int64_t> ratecat;
         const std::string t = precision == 8 ? runTree<double>(ctx, codes, nSeqs, nPos, opt, meLengths != 0, nBootstrap, uniqueFirst, alnNext, nAll, names, ll, rates, ratecat, gtrOut)
