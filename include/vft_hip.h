@@ -67,6 +67,9 @@ typedef struct {
 int vft_create(vft_ctx **out, const vft_config *cfg);
 int vft_destroy(vft_ctx *ctx);
 const char *vft_last_error(const vft_ctx *ctx);
+/* Tests and tools: out[0] = the device and pinned-host allocations the context owns at the moment, out[1] = their bytes as
+   requested.  (Buffers from vft_device_malloc / vft_host_malloc belong to the caller and are not counted.) */
+int vft_allocation_count(vft_ctx *ctx, int64_t out[2]);
 /* hipStream_t to launch on (NULL = the context's own stream).  Lets a caller use torch's current stream. */
 int vft_set_stream(vft_ctx *ctx, void *hip_stream);
 int vft_synchronize(vft_ctx *ctx);

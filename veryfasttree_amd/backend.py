@@ -26,7 +26,7 @@ I64 = C.c_int64
 I32 = C.c_int32
 
 EXPORTS = [
-    "vft_device_malloc", "vft_device_free", "vft_device_upload", "vft_create", "vft_destroy", "vft_last_error", "vft_set_stream", "vft_synchronize", "vft_upload_leaves",
+    "vft_device_malloc", "vft_device_free", "vft_device_upload", "vft_create", "vft_destroy", "vft_allocation_count", "vft_last_error", "vft_set_stream", "vft_synchronize", "vft_upload_leaves",
     "vft_set_distance_matrix", "vft_set_transition_matrix", "vft_set_rates", "vft_set_ml_limits", "vft_set_jc_exact", "vft_set_parents",
     "vft_set_node_scalars", "vft_get_node_scalars", "vft_set_out_distances", "vft_get_out_distances", "vft_out_distance_mirror", "vft_set_max_node",
     "vft_profile_upload", "vft_profile_download", "vft_profile_nvectors", "vft_average_profiles", "vft_out_profile_full", "vft_out_profile_partial", "vft_out_profile_finish",
@@ -746,6 +746,12 @@ class HipProfileOps:
         self._chk(self.lib.vft_merge_hits_batch(self.ctx, P(d_all), I32(n_lists), I32(n_seeds), I32(k), _ptr(hits),
                                                 P(d_out) if d_out else None))
         return hits
+
+    def allocation_count(self):
+        """(live device / pinned-host allocations the context owns, their bytes as requested)"""
+        out = (I64 * 2)()
+        self._chk(self.lib.vft_allocation_count(self.ctx, out))
+        return int(out[0]), int(out[1])
 
     def sweep_info(self):
         info = (I64 * 2)()

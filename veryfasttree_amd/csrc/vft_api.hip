@@ -16,6 +16,7 @@
 #include <chrono>
 
 #include "../../include/vft_hip.h"
+#include "vft_owned.h"
 #define VFT_PAIR_STAGE_CAP 2048   // = the longest list the workgroup-per-pair kernels take
 #define VFT_SMALL_BYTES_ (256u << 10)   // = VFT_SMALL_BYTES below: what goes through the host-mapped ring
 #include "vft_kernels_ml.h"
@@ -35,6 +36,7 @@ VFT_ML_LONG_INSTANCES(extern)    // compiled in vft_ml_kernels_long.hip
 VFT_WALK_SERVER_INSTANCES(extern)   // compiled in vft_walk_kernels.hip
 
 struct vft_ctx {
+    VftOwned own;   // every device and pinned-host allocation of the context (vft_owned.h)
     vft_config cfg;
     VftDims d;
     hipStream_t stream = nullptr, ownStream = nullptr;
@@ -86,35 +88,27 @@ struct vft_ctx {
     double2 *qTab[2] = {nullptr, nullptr};
     void *qPT[2] = {nullptr, nullptr};   // amino acids: per-(column, target code) piece table of the query (vft_kernels_aa.h)
     size_t aaLds = 0;                    // dynamic LDS of k_sweep_aa, 0 = alignment too long for it (generic kernels)
-    // sweep outputs
-    void *swDist = nullptr, *swWeight = nullptr, *swCrit = nullptr;
-    void *partMin = nullptr, *partMax = nullptr;
-    int nPart = 0;
-    // select scratch
-    SelectState *sel = nullptr;
-    unsigned int *slices = nullptr;
-    uint64_t *candKey = nullptr;
-    int32_t *candId = nullptr;
-    char *dRes = nullptr;    // SelectHeader followed by the k hit records
-    char *hRes = nullptr;    // pinned, device-mapped host mirror of dRes, written by the last workgroup of k_select_rank (zero-copy)
-    char *hResDev = nullptr; // device address of hRes
-    // One set of sweep-result + selection buffers per seed of a batch (vft_sweep_batch); slot 0 aliases the members
-    // above, further slots are allocated on first use.
+    // One set of sweep-result + selection buffers per seed of a batch (vft_sweep_batch): slot 0, which the single-seed calls use
+    // too, is made by vft_create, further slots on first use (ensure_slots).
     struct SweepSlotHost {
-        void *swDist = nullptr, *swWeight = nullptr, *swCrit = nullptr, *partMin = nullptr, *partMax = nullptr;
+        void *swDist = nullptr, *swWeight = nullptr, *swCrit = nullptr;   // sweep outputs
+        void *partMin = nullptr, *partMax = nullptr;
+        // select scratch
         SelectState *sel = nullptr;
         unsigned int *slices = nullptr;
         uint64_t *candKey = nullptr;
         int32_t *candId = nullptr;
-        char *dRes = nullptr, *hRes = nullptr, *hResDev = nullptr;
+        char *dRes = nullptr;    // SelectHeader followed by the k hit records
+        char *hRes = nullptr;    // pinned, device-mapped host mirror of dRes, written by the last workgroup of k_select_rank (zero-copy)
+        char *hResDev = nullptr; // device address of hRes
         int nPart = 0;
-        // the seed's staged query (nt without a distance matrix; slot 0 uses the context's qW[0] ...)
+        // the seed's staged query (nt without a distance matrix); slot 0's are the context's qW[0] ..., not allocations of its own
         void *qW = nullptr, *qF = nullptr;
         uint8_t *qC = nullptr;
         uint4 *qEnc = nullptr;
         double2 *qTab = nullptr;
     };
-    std::vector<SweepSlotHost> slots;
+    std::vector<SweepSlotHost> slots;   // never moves (ensure_slots)
     void *mqBuf = nullptr;        // interleaved queries of the profile-seed groups of a batch (QuerySlot::mq): VFT_MQ_GROUPS groups
     size_t mqGroupBytes = 0;
     char *dMerge = nullptr, *hMerge = nullptr, *hMergeDev = nullptr;   // result blocks of vft_merge_hits_batch
@@ -181,7 +175,6 @@ struct vft_ctx {
         uint32_t acked = 0;     // every command up to this one has been answered by all six workgroups
         int stride = 8;         // VFT_DEBUG_WALK_SERVER_STRIDE: 8 = the six workgroups on one XCD, 1 = on six
         bool disabled = false;  // VFT_DEBUG_NO_WALK_SERVER
-        bool allocated = false; // every buffer of the server exists (set behind the last allocation of the first start)
         bool scoredist = false; // logCorrect's flavour of the walk (bit 21 of every command: the workgroups log-correct their distance for a dual command that may follow)
         bool wantWeight[VFT_WS_RING] = {};   // slot seq % RING: the command in it asked for the pairs' weights too (vft_walk_submit_w)
     } ws;
@@ -241,26 +234,78 @@ static int fail(vft_ctx *c, int code, const char *fmt, ...) {
         if (e_ != hipSuccess) return fail(c, VFT_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e_)); \
     } while (0)
 
-template <typename T>
-static hipError_t dalloc(T **p, size_t n) {
-    if (n == 0) n = 1;
-    hipError_t e = hipMalloc((void **) p, n * sizeof(T));
-    return e;
+// ---------------------------------------------------------------------------------------------- allocations (vft_owned.h)
+int vft_raw_device_alloc(void **p, size_t bytes, bool fineGrained) {
+    const hipError_t e = fineGrained ? hipExtMallocWithFlags(p, bytes, hipDeviceMallocFinegrained) : hipMalloc(p, bytes);
+    if (e != hipSuccess) (void) hipGetLastError();
+    return (int) e;
 }
-static hipError_t dallocb(void **p, size_t bytes) { return hipMalloc(p, bytes ? bytes : 1); }
+int vft_raw_device_free(void *p) { return (int) hipFree(p); }
+int vft_raw_host_alloc(void **host, void **dev, size_t bytes) {
+    hipError_t e = hipHostMalloc(host, bytes, hipHostMallocMapped);
+    if (e == hipSuccess && (e = hipHostGetDevicePointer(dev, *host, 0)) != hipSuccess) (void) hipHostFree(*host);
+    if (e != hipSuccess) (void) hipGetLastError();
+    return (int) e;
+}
+int vft_raw_host_free(void *host) { return (int) hipHostFree(host); }
+
+// Device memory of the context.  fill >= 0: every byte is set to it right behind the allocation - on the NULL stream (the caller
+// orders that before the context's stream, as vft_create does) or on the context's stream - and an allocation whose fill fails is
+// released again.
+enum OwnFillOn { ON_NULL_STREAM, ON_STREAM };
+template <typename T>
+static int own_dev(vft_ctx *c, T **p, size_t bytes, int fill = -1, OwnFillOn on = ON_NULL_STREAM, bool fineGrained = false) {
+    const bool onStream = on == ON_STREAM;
+    if (!c->own.device(p, bytes, fineGrained))
+        return fail(c, VFT_ERR_HIP, "device allocation of %zu bytes failed: %s", bytes, hipGetErrorString((hipError_t) c->own.err));
+    if (fill < 0) return VFT_OK;
+    const hipError_t e = onStream ? hipMemsetAsync(*p, fill, bytes, c->stream) : hipMemset(*p, fill, bytes);
+    if (e == hipSuccess) return VFT_OK;
+    c->own.release(p);
+    return fail(c, VFT_ERR_HIP, "hipMemset of %zu bytes failed: %s", bytes, hipGetErrorString(e));
+}
+// fine-grained device memory (the walk server's device mailbox), zeroed on the NULL stream
+template <typename T>
+static int own_dev_fine(vft_ctx *c, T **p, size_t bytes) { return own_dev(c, p, bytes, 0, ON_NULL_STREAM, true); }
+// mapped pinned host memory of the context and its device address; the first `zeroed` bytes are cleared
+template <typename H, typename D>
+static int own_host(vft_ctx *c, H **h, D **d, size_t bytes, size_t zeroed) {
+    if (c->own.host(h, d, bytes, zeroed)) return VFT_OK;
+    return fail(c, VFT_ERR_HIP, "mapped host allocation of %zu bytes failed: %s", bytes, hipGetErrorString((hipError_t) c->own.err));
+}
+// The allocations of a subsystem as one group: `make` creates all of them, or - after a failure anywhere in it - the group is rolled back
+// (their members are null again) and the subsystem does not exist.
+template <typename F>
+static int own_group(vft_ctx *c, F make) {
+    const size_t mark = c->own.mark();
+    const int r = make();
+    if (r != VFT_OK) {
+        if (c->stream) (void) hipStreamSynchronize(c->stream);   // (fills may be queued on it)
+        c->own.rollback(mark);
+    }
+    return r;
+}
+#define OWNCHK(call)                  \
+    do {                              \
+        if (int r_ = (call)) return r_; \
+    } while (0)
+
+// a buffer that is replaced by a larger one when a request outgrows it (the stream may still be reading the old one)
+template <typename T>
+static int own_regrow(vft_ctx *c, T **p, size_t *have, size_t want) {
+    if (*p) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->own.release(p);
+        *have = 0;
+    }
+    OWNCHK(own_dev(c, p, want));
+    *have = want;
+    return VFT_OK;
+}
 
 static int ensure_scratch(vft_ctx *c, size_t bytes) {
     if (bytes <= c->scratchBytes) return VFT_OK;
-    if (c->scratch) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(c->scratch));
-        c->scratch = nullptr;
-        c->scratchBytes = 0;
-    }
-    size_t want = bytes + bytes / 2 + 4096;
-    HIPCHK(c, hipMalloc(&c->scratch, want));
-    c->scratchBytes = want;
-    return VFT_OK;
+    return own_regrow(c, &c->scratch, &c->scratchBytes, bytes + bytes / 2 + 4096);
 }
 
 template <typename REAL>
@@ -319,7 +364,6 @@ static QueryBuf<REAL> qbuf(const vft_ctx *c, int which) {
 // the staged query of a batch slot
 template <typename REAL>
 static QueryBuf<REAL> qbuf_slot(const vft_ctx *c, int slot) {
-    if (slot == 0) return qbuf<REAL>(c, 0);
     const vft_ctx::SweepSlotHost &h = c->slots[(size_t) slot];
     QueryBuf<REAL> q;
     q.w = (REAL *) h.qW;
@@ -449,31 +493,22 @@ static int io_alloc(vft_ctx *c, size_t bytes, char **host, char **dev) {
 
 
 static int raise_pair_kernel_lds(vft_ctx *c);   // defined next to the kernels it configures
+#define VFT_MAX_SLOTS 64                        // the seeds of the largest batch (vft_sweep_batch)
+static int ensure_slots(vft_ctx *c, int count);
 
 // ---------------------------------------------------------------------------------------------- life cycle
-extern "C" int vft_create(vft_ctx **out, const vft_config *cfg) {
-    if (!out || !cfg) return VFT_ERR_INVALID;
-    *out = nullptr;
-    if (g_launchTrace) signal(SIGABRT, launch_trace_abort);
-    vft_ctx *c = new (std::nothrow) vft_ctx();
-    if (!c) return VFT_ERR_INVALID;
-    c->cfg = *cfg;
-    auto bail = [&](int code) {
-        // keep the context alive so the caller can read the error text
-        *out = c;
-        return code;
-    };
+static int context_init(vft_ctx *c, const vft_config *cfg) {
     if ((cfg->precision != 4 && cfg->precision != 8) || (cfg->n_codes != 4 && cfg->n_codes != 20) || cfg->n_seqs < 1 ||
         cfg->n_pos < 1 || cfg->max_nodes < cfg->n_seqs || cfg->max_nodes >= (1ll << 31))
-        return bail(fail(c, VFT_ERR_INVALID, "vft_create: bad configuration"));
+        return fail(c, VFT_ERR_INVALID, "vft_create: bad configuration");
     // a tile's vector stream is addressed with 32-bit byte offsets (k_sweep_nt): 64 nodes x nPos x nCodes reals < 4 GiB
     if ((double) (cfg->n_pos + VFT_CHUNK) * VFT_TILE * cfg->n_codes * cfg->precision >= 4294967296.0)
-        return bail(fail(c, VFT_ERR_INVALID, "vft_create: alignment too long (%lld columns)", (long long) cfg->n_pos));
+        return fail(c, VFT_ERR_INVALID, "vft_create: alignment too long (%lld columns)", (long long) cfg->n_pos);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return bail(fail(c, VFT_ERR_HIP, "vft_create: no HIP device (this backend has no CPU fallback)"));
-    if (cfg->device < 0 || cfg->device >= ndev) return bail(fail(c, VFT_ERR_INVALID, "vft_create: bad device ordinal"));
-    if (hipSetDevice(cfg->device) != hipSuccess) return bail(fail(c, VFT_ERR_HIP, "hipSetDevice failed"));
+        return fail(c, VFT_ERR_HIP, "vft_create: no HIP device (this backend has no CPU fallback)");
+    if (cfg->device < 0 || cfg->device >= ndev) return fail(c, VFT_ERR_INVALID, "vft_create: bad device ordinal");
+    if (hipSetDevice(cfg->device) != hipSuccess) return fail(c, VFT_ERR_HIP, "hipSetDevice failed");
     c->rs = (size_t) cfg->precision;
     VftDims &d = c->d;
     d.nSeqs = cfg->n_seqs;
@@ -492,51 +527,45 @@ extern "C" int vft_create(vft_ctx **out, const vft_config *cfg) {
     const size_t rs = c->rs;
     const int64_t N = d.nTiles * VFT_TILE;   // padded node count
     const int64_t nPosPad = (int64_t) d.nChunk * VFT_CHUNK;
-#define CR(call)                                                                            \
-    do {                                                                                    \
-        hipError_t e_ = (call);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return bail(fail(c, VFT_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_))); \
-    } while (0)
-    CR(hipStreamCreateWithFlags(&c->ownStream, hipStreamNonBlocking));
+    HIPCHK(c, hipStreamCreateWithFlags(&c->ownStream, hipStreamNonBlocking));
     c->stream = c->ownStream;
-    CR(dalloc(&c->leafT, (size_t) c->nLeafTiles * d.nChunk * VFT_TILE));
-    CR(dallocb(&c->profW, (size_t) c->nProfTiles * d.nPosPad * VFT_TILE * rs));
-    CR(dallocb(&c->profF, (size_t) c->nProfTiles * d.nPosPad * VFT_TILE * d.nCodes * rs));
-    CR(dalloc(&c->profC, (size_t) c->nProfTiles * d.nChunk * VFT_TILE));
-    CR(hipMemset(c->profW, 0, (size_t) c->nProfTiles * d.nPosPad * VFT_TILE * rs));
-    CR(dalloc(&c->colMask, (size_t) c->nProfTiles * d.nPosPad));
-    CR(hipMemset(c->colMask, 0, (size_t) c->nProfTiles * d.nPosPad * sizeof(ColMask)));
-    CR(dalloc(&c->colOff, (size_t) c->nProfTiles * d.nPosPad));
-    CR(hipMemset(c->colOff, 0, (size_t) c->nProfTiles * d.nPosPad * sizeof(ColOff)));
+    OWNCHK(own_dev(c, &c->leafT, (size_t) c->nLeafTiles * d.nChunk * VFT_TILE * sizeof(uint4)));
+    OWNCHK(own_dev(c, &c->profW, (size_t) c->nProfTiles * d.nPosPad * VFT_TILE * rs, 0));
+    OWNCHK(own_dev(c, &c->profF, (size_t) c->nProfTiles * d.nPosPad * VFT_TILE * d.nCodes * rs));
+    OWNCHK(own_dev(c, &c->profC, (size_t) c->nProfTiles * d.nChunk * VFT_TILE * sizeof(uint4), 0x7F));
+    OWNCHK(own_dev(c, &c->colMask, (size_t) c->nProfTiles * d.nPosPad * sizeof(ColMask), 0));
+    OWNCHK(own_dev(c, &c->colOff, (size_t) c->nProfTiles * d.nPosPad * sizeof(ColOff), 0));
     c->hParent.assign((size_t) N, 0);
     for (int64_t i = 0; i < cfg->max_nodes; i++) c->hParent[(size_t) i] = -1;
-    CR(dalloc(&c->tileMask, (size_t) d.nTiles));
-    CR(hipMemset(c->profC, 0x7F, (size_t) c->nProfTiles * d.nChunk * VFT_TILE * sizeof(uint4)));
-    CR(dalloc(&c->parent, (size_t) N));
-    CR(dalloc(&c->nOutActive, (size_t) N));
-    // padding ids beyond max_nodes are permanently inactive
-    {
-        std::vector<int32_t> par((size_t) N, 0);
-        for (int64_t i = 0; i < cfg->max_nodes; i++) par[(size_t) i] = -1;
-        CR(hipMemcpy(c->parent, par.data(), (size_t) N * 4, hipMemcpyHostToDevice));
-    }
-    CR(hipMemset(c->nOutActive, 0, (size_t) N * 4));
-    void **reals[] = {&c->diameter, &c->selfweight, &c->selfdist, &c->outDist, &c->swDist, &c->swWeight, &c->swCrit};
-    for (void **p : reals) {
-        CR(dallocb(p, (size_t) N * rs));
-        CR(hipMemset(*p, 0, (size_t) N * rs));
-    }
-    CR(dallocb(&c->outW, (size_t) d.nPos * rs));
-    CR(dallocb(&c->outF, (size_t) d.nPos * d.nCodes * rs));
-    CR(dallocb(&c->outCD, (size_t) d.nPos * d.nCodes * rs));
+    OWNCHK(own_dev(c, &c->tileMask, (size_t) d.nTiles * sizeof(unsigned long long)));
+    OWNCHK(own_dev(c, &c->parent, (size_t) N * 4));
+    OWNCHK(own_dev(c, &c->nOutActive, (size_t) N * 4, 0));
+    // padding ids beyond max_nodes are permanently inactive (hParent holds exactly that)
+    HIPCHK(c, hipMemcpy(c->parent, c->hParent.data(), (size_t) N * 4, hipMemcpyHostToDevice));
+    void **reals[] = {&c->diameter, &c->selfweight, &c->selfdist, &c->outDist};
+    for (void **p : reals) OWNCHK(own_dev(c, p, (size_t) N * rs, 0));
+    // Slot 0 right here: its three per-node arrays belong beside the arena's four (the order they have always been allocated in).
+    // Allocated behind the small staging buffers below instead, the benchmark's step was 1 % slower (profiles/ctx_allocations_wallclock.txt).
+    c->hitsCap = VFT_CAND_CAP;
+    OWNCHK(ensure_slots(c, 1));
+    OWNCHK(own_dev(c, &c->outW, (size_t) d.nPos * rs));
+    OWNCHK(own_dev(c, &c->outF, (size_t) d.nPos * d.nCodes * rs));
+    OWNCHK(own_dev(c, &c->outCD, (size_t) d.nPos * d.nCodes * rs));
     for (int q = 0; q < 2; q++) {
-        CR(dallocb(&c->qW[q], (size_t) nPosPad * rs));
-        CR(dallocb(&c->qF[q], (size_t) nPosPad * d.nCodes * rs));
-        CR(dalloc(&c->qC[q], (size_t) nPosPad));
-        CR(dalloc(&c->qEnc[q], (size_t) d.nChunk));
-        CR(dalloc(&c->qTab[q], (size_t) nPosPad * 5));
-        CR(dallocb(&c->qPT[q], d.nCodes == 20 ? (size_t) nPosPad * 20 * rs : 1));
+        OWNCHK(own_dev(c, &c->qW[q], (size_t) nPosPad * rs));
+        OWNCHK(own_dev(c, &c->qF[q], (size_t) nPosPad * d.nCodes * rs));
+        OWNCHK(own_dev(c, &c->qC[q], (size_t) nPosPad));
+        OWNCHK(own_dev(c, &c->qEnc[q], (size_t) d.nChunk * sizeof(uint4)));
+        OWNCHK(own_dev(c, &c->qTab[q], (size_t) nPosPad * 5 * sizeof(double2)));
+        OWNCHK(own_dev(c, &c->qPT[q], d.nCodes == 20 ? (size_t) nPosPad * 20 * rs : 1));
+    }
+    {   // slot 0's staged query is the context's node query, not allocations of its own (ensure_slots makes none for it)
+        vft_ctx::SweepSlotHost &s0 = c->slots[0];
+        s0.qW = c->qW[0];
+        s0.qF = c->qF[0];
+        s0.qC = c->qC[0];
+        s0.qEnc = c->qEnc[0];
+        s0.qTab = c->qTab[0];
     }
     if (d.nCodes == 20) {
         const size_t need = (((size_t) nPosPad * 20 * rs + 15) & ~(size_t) 15) + (size_t) nPosPad * 8 + (size_t) 2 * VFT_CHUNK * VFT_TILE * 16;
@@ -544,73 +573,32 @@ extern "C" int vft_create(vft_ctx **out, const vft_config *cfg) {
             c->aaLds = need;
             if (need > (48u << 10)) {
                 if (rs == 4) {
-                    CR(hipFuncSetAttribute((const void *) k_sweep_aa<float, MODE_CRIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) need));
-                    CR(hipFuncSetAttribute((const void *) k_sweep_aa<float, MODE_OUTDIST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) need));
+                    HIPCHK(c, hipFuncSetAttribute((const void *) k_sweep_aa<float, MODE_CRIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) need));
+                    HIPCHK(c, hipFuncSetAttribute((const void *) k_sweep_aa<float, MODE_OUTDIST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) need));
                 } else {
-                    CR(hipFuncSetAttribute((const void *) k_sweep_aa<double, MODE_CRIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) need));
-                    CR(hipFuncSetAttribute((const void *) k_sweep_aa<double, MODE_OUTDIST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) need));
+                    HIPCHK(c, hipFuncSetAttribute((const void *) k_sweep_aa<double, MODE_CRIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) need));
+                    HIPCHK(c, hipFuncSetAttribute((const void *) k_sweep_aa<double, MODE_OUTDIST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) need));
                 }
             }
         }
     }
-    c->nPart = (int) cdiv(N, VFT_WG);
-    CR(dallocb(&c->partMin, (size_t) c->nPart * 8));
-    CR(dallocb(&c->partMax, (size_t) c->nPart * 8));
-    CR(dalloc(&c->sel, 1));
-    CR(hipMemset(c->sel, 0, sizeof(SelectState)));
-    CR(dalloc(&c->slices, (size_t) VFT_NBINS));
-    CR(hipMemset(c->slices, 0, (size_t) VFT_NBINS * 4));   // (the selection's histogram is zero between selections: k_select_rank's last workgroup leaves it so)
-    CR(dalloc(&c->candKey, (size_t) VFT_CAND_CAP));
-    CR(hipMemset(c->candKey, 0, (size_t) VFT_CAND_CAP * 8));
-    CR(dalloc(&c->candId, (size_t) VFT_CAND_CAP));
-    CR(hipMemset(c->candId, 0, (size_t) VFT_CAND_CAP * 4));
-    c->hitsCap = VFT_CAND_CAP;
-    CR(dallocb((void **) &c->dRes, sizeof(SelectHeader) + (size_t) c->hitsCap * sizeof(vft_hit_f64)));
-    CR(hipHostMalloc((void **) &c->hRes, sizeof(SelectHeader) + (size_t) c->hitsCap * sizeof(vft_hit_f64), hipHostMallocMapped));
-    CR(hipHostGetDevicePointer((void **) &c->hResDev, c->hRes, 0));
-    memset(c->hRes, 0, sizeof(SelectHeader));
-    {
-        vft_ctx::SweepSlotHost s0;
-        s0.swDist = c->swDist;
-        s0.swWeight = c->swWeight;
-        s0.swCrit = c->swCrit;
-        s0.partMin = c->partMin;
-        s0.partMax = c->partMax;
-        s0.sel = c->sel;
-        s0.slices = c->slices;
-        s0.candKey = c->candKey;
-        s0.candId = c->candId;
-        s0.dRes = c->dRes;
-        s0.hRes = c->hRes;
-        s0.hResDev = c->hResDev;
-        c->slots.assign(1, s0);
-    }
     // [0]: the stream's completion flag
-    CR(hipHostMalloc((void **) &c->hFlag, 512, hipHostMallocMapped));
-    CR(hipHostGetDevicePointer((void **) &c->dFlag, c->hFlag, 0));
-    memset(c->hFlag, 0, 512);
-    CR(dalloc(&c->doneCtr, 65));   // [0]: top level / single-level users, [1..64]: slots of vft_publish_staged
-    CR(hipMalloc(&c->pairStage, 3 * VFT_PAIR_STAGE_CAP * sizeof(double)));   // staging of short pair lists' results (vft_publish_staged)
-    CR(hipMalloc(&c->pairIn, VFT_SMALL_BYTES_));   // device copy of a short list's inputs
-    CR(hipMemset(c->doneCtr, 0, 65 * 4));
-    CR(hipHostMalloc((void **) &c->hIO, c->ioCap, hipHostMallocMapped));
-    CR(hipHostGetDevicePointer((void **) &c->dIO, c->hIO, 0));
-    CR(hipHostMalloc(&c->hOutDist, (size_t) N * rs, hipHostMallocMapped));
-    CR(hipHostGetDevicePointer(&c->dOutDistM, c->hOutDist, 0));
-    CR(hipHostMalloc((void **) &c->hNOut, (size_t) N * 4, hipHostMallocMapped));
-    CR(hipHostGetDevicePointer((void **) &c->dNOutM, c->hNOut, 0));
-    memset(c->hOutDist, 0, (size_t) N * rs);
-    memset(c->hNOut, 0, (size_t) N * 4);
-    for (int i = 0; i < 4; i++) CR(dallocb(&c->dm[i], (size_t) 21 * 20 * 8));
-    for (int i = 0; i < 6; i++) CR(dallocb(&c->tm[i], (size_t) 21 * 20 * 8));
-    CR(dallocb(&c->rates, (size_t) VFT_MAXRATES * 8));
-    CR(dalloc(&c->ratecat, (size_t) d.nPos));
+    OWNCHK(own_host(c, &c->hFlag, &c->dFlag, 512, 512));
+    OWNCHK(own_dev(c, &c->doneCtr, 65 * 4, 0));   // [0]: top level / single-level users, [1..64]: slots of vft_publish_staged
+    OWNCHK(own_dev(c, &c->pairStage, 3 * VFT_PAIR_STAGE_CAP * sizeof(double)));   // staging of short pair lists' results (vft_publish_staged)
+    OWNCHK(own_dev(c, &c->pairIn, VFT_SMALL_BYTES_));   // device copy of a short list's inputs
+    OWNCHK(own_host(c, &c->hIO, &c->dIO, c->ioCap, 0));
+    OWNCHK(own_host(c, &c->hOutDist, &c->dOutDistM, (size_t) N * rs, (size_t) N * rs));
+    OWNCHK(own_host(c, &c->hNOut, &c->dNOutM, (size_t) N * 4, (size_t) N * 4));
+    for (int i = 0; i < 4; i++) OWNCHK(own_dev(c, &c->dm[i], (size_t) 21 * 20 * 8));
+    for (int i = 0; i < 6; i++) OWNCHK(own_dev(c, &c->tm[i], (size_t) 21 * 20 * 8));
+    OWNCHK(own_dev(c, &c->rates, (size_t) VFT_MAXRATES * 8));
+    OWNCHK(own_dev(c, &c->ratecat, (size_t) d.nPos * 4, 0));
     {
         // one rate category with rate 1.0 (Rates(1, nPos) in the NJ constructor, NJ.tcc:226)
         double one64 = 1.0;
         float one32 = 1.0f;
-        CR(hipMemcpy(c->rates, rs == 4 ? (void *) &one32 : (void *) &one64, rs, hipMemcpyHostToDevice));
-        CR(hipMemset(c->ratecat, 0, (size_t) d.nPos * 4));
+        HIPCHK(c, hipMemcpy(c->rates, rs == 4 ? (void *) &one32 : (void *) &one64, rs, hipMemcpyHostToDevice));
         c->nRates = 1;
     }
     if (cfg->precision == 8) {
@@ -618,79 +606,46 @@ extern "C" int vft_create(vft_ctx **out, const vft_config *cfg) {
         c->minRel = 2.5e-9;
         c->fpostTol = 1e-20;
     }
-    CR(hipEventCreate(&c->ev0));
-    CR(hipEventCreate(&c->ev1));
-    if (int r = raise_pair_kernel_lds(c)) return bail(r);
+    HIPCHK(c, hipEventCreate(&c->ev0));
+    HIPCHK(c, hipEventCreate(&c->ev1));
+    OWNCHK(raise_pair_kernel_lds(c));
     // The hipMemsets above run on the NULL stream and need not have finished when they return (device memory), and the context's own
     // stream is a non-blocking one: nothing orders them before its first kernel.  Wait here, once.
-    CR(hipDeviceSynchronize());
-#undef CR
-    *out = c;
+    HIPCHK(c, hipDeviceSynchronize());
     return VFT_OK;
+}
+
+extern "C" int vft_create(vft_ctx **out, const vft_config *cfg) {
+    if (!out || !cfg) return VFT_ERR_INVALID;
+    *out = nullptr;
+    if (g_launchTrace) signal(SIGABRT, launch_trace_abort);
+    vft_ctx *c = new (std::nothrow) vft_ctx();
+    if (!c) return VFT_ERR_INVALID;
+    c->cfg = *cfg;
+    *out = c;   // also after a failure: the caller reads the error text, and vft_destroy releases what has been made
+    return context_init(c, cfg);
 }
 
 extern "C" int vft_destroy(vft_ctx *c) {
     if (!c) return VFT_OK;
     (void) walk_server_retire(c);
-    if (c->ws.stream) {
-        hipStreamDestroy(c->ws.stream);
-        if (c->ws.mailOnDevice) hipFree(c->ws.dMail);
-        else hipHostFree(c->ws.hMail);
-        hipHostFree(c->ws.hRes);
-        hipFree(c->ws.dFlags);
-    }
-    (void) vft_exhaustive_destroy(c);
-    if (c->blen) hipFree(c->blen);
-    if (c->mlLongWs) hipFree(c->mlLongWs);
-    if (c->opHist) hipFree(c->opHist);
-    if (c->refDone) hipFree(c->refDone);
-    if (c->pendBase) hipFree(c->pendBase);
-    if (c->pendIdsDev) hipFree(c->pendIdsDev);
-    if (c->mlIs) hipFree(c->mlIs);
-    if (c->mlC) hipFree(c->mlC);
-    if (c->mlW) hipFree(c->mlW);
-    if (c->mlF) hipFree(c->mlF);
-    if (c->mlEvals) hipFree(c->mlEvals);
-    if (c->dMerge) hipFree(c->dMerge);
-    if (c->hMerge) hipHostFree(c->hMerge);
-    if (c->mqBuf) hipFree(c->mqBuf);
-    for (size_t i = 1; i < c->slots.size(); i++) {   // slot 0 aliases members freed below
-        vft_ctx::SweepSlotHost &h = c->slots[i];
-        void *dev[] = {h.swDist, h.swWeight, h.swCrit, h.partMin, h.partMax, h.sel, h.slices, h.candKey, h.candId, h.dRes, h.qW, h.qF, h.qC, h.qEnc, h.qTab};
-        for (void *p: dev)
-            if (p) hipFree(p);
-        if (h.hRes) hipHostFree(h.hRes);
-    }
     if (c->ownStream) hipStreamSynchronize(c->ownStream);
-    void *ptrs[] = {c->tileMask, c->colMask, c->colOff, c->leafT, c->profC, c->profW, c->profF, c->parent, c->nOutActive, c->diameter, c->selfweight,
-                    c->selfdist, c->outDist, c->outW, c->outF, c->outCD, c->qW[0], c->qW[1], c->qF[0], c->qF[1],
-                    c->qC[0], c->qC[1], c->qEnc[0], c->qEnc[1], c->qTab[0], c->qTab[1], c->qPT[0], c->qPT[1], c->swDist, c->swWeight, c->swCrit,
-                    c->partMin, c->partMax, c->sel, c->slices, c->candKey, c->candId, c->dRes, c->dm[0],
-                    c->dm[1], c->dm[2], c->dm[3], c->tm[0], c->tm[1], c->tm[2], c->tm[3], c->tm[4], c->tm[5],
-                    c->rates, c->ratecat, c->scratch};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
-    if (c->hRes) hipHostFree(c->hRes);
-    if (c->hIO) hipHostFree(c->hIO);
-    if (c->hFlag) hipHostFree(c->hFlag);
-    if (c->doneCtr) hipFree(c->doneCtr);
-    for (void *p : {c->thHits, c->thStD, c->thStC, (void *) c->thLen, (void *) c->thStJ, (void *) c->thMark, (void *) c->thDone, (void *) c->thSorted,
-                    c->njState, c->njVisD, (void *) c->njVisJ, (void *) c->njTop, (void *) c->njAge, (void *) c->njLogDev, (void *) c->njClaim,
-                    (void *) c->njLogNode, (void *) c->njLogStamp, c->njLogOut, (void *) c->njSlotI, c->njSlotR, (void *) c->njCandI, c->njCandR})
-        if (p) hipFree(p);
-    if (c->njLogHost) hipHostFree(c->njLogHost);
-    if (c->njStatusHost) hipHostFree(c->njStatusHost);
-    if (c->pairStage) hipFree(c->pairStage);
-    if (c->pairIn) hipFree(c->pairIn);
-    if (c->hOutDist) hipHostFree(c->hOutDist);
-    if (c->hNOut) hipHostFree(c->hNOut);
+    if (c->ws.stream) hipStreamSynchronize(c->ws.stream);
+    c->own.release_all();
     for (hipEvent_t e : c->kev) hipEventDestroy(e);
     if (c->ev0) hipEventDestroy(c->ev0);
     if (c->ev1) hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->dlEv)
         if (e) hipEventDestroy(e);
+    if (c->ws.stream) hipStreamDestroy(c->ws.stream);
     if (c->ownStream) hipStreamDestroy(c->ownStream);
     delete c;
+    return VFT_OK;
+}
+
+extern "C" int vft_allocation_count(vft_ctx *c, int64_t out[2]) {
+    if (!c || !out) return VFT_ERR_INVALID;
+    c->own.count(out);
     return VFT_OK;
 }
 
@@ -1034,12 +989,22 @@ static CommitPlan commit_plan(const vft_ctx *c, int64_t n) {
 static int ensure_ml_rows(vft_ctx *c) {
     if (c->mlIs) return VFT_OK;
     const size_t nodes = (size_t) (c->d.maxNodes - c->d.nSeqs), cols = nodes * (size_t) c->d.nPos;
-    HIPCHK(c, hipMalloc((void **) &c->mlW, cols * c->rs));
-    HIPCHK(c, hipMalloc((void **) &c->mlF, cols * (size_t) c->d.nCodes * c->rs));
-    HIPCHK(c, hipMalloc((void **) &c->mlC, cols));
-    HIPCHK(c, hipMalloc((void **) &c->mlIs, nodes));
-    HIPCHK(c, hipMemsetAsync(c->mlIs, 0, nodes, c->stream));
-    return VFT_OK;
+    return own_group(c, [&]() -> int {
+        OWNCHK(own_dev(c, &c->mlW, cols * c->rs));
+        OWNCHK(own_dev(c, &c->mlF, cols * (size_t) c->d.nCodes * c->rs));
+        OWNCHK(own_dev(c, &c->mlC, cols));
+        return own_dev(c, &c->mlIs, nodes, 0, ON_STREAM);
+    });
+}
+
+#define VFT_PEND_MAX 64
+// the stash of the joins whose tiles have not been rebuilt yet (vft_join_fused, the join engine) and the device copy of their ids
+static int ensure_pend(vft_ctx *c) {
+    if (c->pendBase) return VFT_OK;
+    return own_group(c, [&]() -> int {
+        OWNCHK(own_dev(c, &c->pendBase, commit_plan(c, VFT_PEND_MAX).totalB + 512));
+        return own_dev(c, &c->pendIdsDev, VFT_PEND_MAX * sizeof(int64_t));
+    });
 }
 
 // a node rewritten through the tile streams no longer has a dense ML row
@@ -1093,7 +1058,6 @@ static int commit_nodes(vft_ctx *c, const CommitPlan &plan, const int64_t *hNode
     return VFT_OK;
 }
 
-#define VFT_PEND_MAX 64
 // rebuilds the tile streams of the nodes joined by vft_join_fused since the last rebuild (their stash slots are intact)
 static int flush_pending(vft_ctx *c) {
     if (c->pend.empty()) return VFT_OK;
@@ -1452,37 +1416,33 @@ extern "C" int vft_walk_server_start(vft_ctx *c) {
     const size_t staticLds = (c->d.nCodes == 20 ? (size_t) 840 * c->rs : 8) + 1024;
     if (lds + staticLds > (160u << 10)) return fail(c, VFT_ERR_STATE, "vft_walk_server_start: alignment too long for one workgroup per pair");
     vft_ctx::WalkServerHost &W = c->ws;
-    // (`allocated` is raised behind the LAST allocation and the synchronisation below: a start that failed anywhere before that -
-    // the flags, the tick block, the mailbox, its device pointer - must not be launched on null pointers by the next call)
-    if (W.stream && !W.allocated) return fail(c, VFT_ERR_STATE, "vft_walk_server_start: an earlier start failed half-way (the walks keep the plain calls)");
+    // The server's buffers are one group and its stream is made behind them: a start that fails anywhere leaves no stream and no
+    // buffer, so a stream means that everything exists.
     if (!W.stream) {
-        HIPCHK(c, hipStreamCreateWithFlags(&W.stream, hipStreamNonBlocking));
-        HIPCHK(c, hipHostMalloc((void **) &W.hRes, (size_t) VFT_WS_RING * VFT_WS_RESG * 8 + 512, hipHostMallocMapped));
-        HIPCHK(c, hipHostGetDevicePointer((void **) &W.dRes, W.hRes, 0));
-        memset(W.hRes, 0, (size_t) VFT_WS_RING * VFT_WS_RESG * 8 + 512);
+        const int r = own_group(c, [&]() -> int {
+            const size_t resBytes = (size_t) VFT_WS_RING * VFT_WS_RESG * 8 + 512;
+            OWNCHK(own_host(c, &W.hRes, &W.dRes, resBytes, resBytes));
+            OWNCHK(own_dev(c, &W.dFlags, 64 * 8, 0));
+            if (!g_wsTicks) {   // (per process: tools read it after the contexts are gone)
+                HIPCHK(c, hipMalloc((void **) &g_wsTicks, 16 * 8));
+                HIPCHK(c, hipMemset(g_wsTicks, 0, 16 * 8));
+            }
+            const size_t mailBytes = (size_t) VFT_WS_RING * VFT_WS_GRAN * 8;
+            int largeBar = 0;
+            if (W.wantDeviceMail) (void) hipDeviceGetAttribute(&largeBar, hipDeviceAttributeIsLargeBar, c->cfg.device);
+            W.mailOnDevice = W.wantDeviceMail && largeBar;
+            if (W.mailOnDevice)   // device memory the CPU writes through the PCIe aperture: the polls stay on the device
+                OWNCHK(own_dev_fine(c, &W.dMail, mailBytes));
+            else
+                OWNCHK(own_host(c, &W.hMail, &W.dMail, mailBytes, mailBytes));
+            HIPCHK(c, hipDeviceSynchronize());
+            HIPCHK(c, hipStreamCreateWithFlags(&W.stream, hipStreamNonBlocking));
+            return VFT_OK;
+        });
+        if (r) return r;
+        if (W.mailOnDevice) W.hMail = W.dMail;
         W.hStatus = W.hRes + (size_t) VFT_WS_RING * VFT_WS_RESG;
         W.dStatus = W.dRes + (size_t) VFT_WS_RING * VFT_WS_RESG;
-        HIPCHK(c, dalloc(&W.dFlags, 64));
-        HIPCHK(c, hipMemset(W.dFlags, 0, 64 * 8));
-        if (!g_wsTicks) {   // (per process: tools read it after the contexts are gone)
-            HIPCHK(c, dalloc(&g_wsTicks, 16));
-            HIPCHK(c, hipMemset(g_wsTicks, 0, 16 * 8));
-        }
-        const size_t mailBytes = (size_t) VFT_WS_RING * VFT_WS_GRAN * 8;
-        int largeBar = 0;
-        if (W.wantDeviceMail) (void) hipDeviceGetAttribute(&largeBar, hipDeviceAttributeIsLargeBar, c->cfg.device);
-        if (W.wantDeviceMail && largeBar) {   // device memory the CPU writes through the PCIe aperture: the polls stay on the device
-            HIPCHK(c, hipExtMallocWithFlags((void **) &W.dMail, mailBytes, hipDeviceMallocFinegrained));
-            HIPCHK(c, hipMemset(W.dMail, 0, mailBytes));
-            W.hMail = W.dMail;
-            W.mailOnDevice = true;
-        } else {
-            HIPCHK(c, hipHostMalloc((void **) &W.hMail, mailBytes, hipHostMallocMapped));
-            HIPCHK(c, hipHostGetDevicePointer((void **) &W.dMail, W.hMail, 0));
-            memset(W.hMail, 0, mailBytes);
-        }
-        HIPCHK(c, hipDeviceSynchronize());
-        W.allocated = true;
     }
     if (int r = wait_stream(c)) return r;   // everything queued on the context's stream has written its rows
     for (int w = 0; w < VFT_WS_NWG; w++) W.hStatus[w] = 0;
@@ -1738,11 +1698,7 @@ extern "C" int vft_join_fused(vft_ctx *c, int64_t i, int64_t j, int64_t newnode,
         return fail(c, VFT_ERR_INVALID, "vft_join_fused: bad arguments (%lld, %lld -> %lld)", (long long) i, (long long) j, (long long) newnode);
     if (c->rowMode) return fail(c, VFT_ERR_STATE, "vft_join_fused belongs to the NJ phase (before vft_set_profile_rows)");
     if (int r = ensure_ml_rows(c)) return r;
-    if (!c->pendBase) {
-        const CommitPlan plan = commit_plan(c, VFT_PEND_MAX);
-        HIPCHK(c, hipMalloc((void **) &c->pendBase, plan.totalB + 512));
-        HIPCHK(c, hipMalloc((void **) &c->pendIdsDev, VFT_PEND_MAX * sizeof(int64_t)));
-    }
+    if (int r = ensure_pend(c)) return r;
     if ((int64_t) c->pend.size() == VFT_PEND_MAX)
         if (int r = flush_pending(c)) return r;
     // host-side bookkeeping of vft_join_nodes
@@ -1813,7 +1769,7 @@ extern "C" int vft_out_profile_full(vft_ctx *c, int64_t n, const int64_t *ids) {
         const bool leafHist = c->cfg.n_codes == 4 && !c->hasDm;
         if (leafHist) {
             const size_t hb = (size_t) c->d.nPosPad * 4 * sizeof(unsigned int);
-            if (!c->opHist) HIPCHK(c, hipMalloc((void **) &c->opHist, hb));
+            if (!c->opHist) OWNCHK(own_dev(c, &c->opHist, hb));
             HIPCHK(c, hipMemsetAsync(c->opHist, 0, hb, c->stream));
             const int64_t nLeafTiles = (c->d.nSeqs + 63) / 64;
             const unsigned gx = (unsigned) std::min<int64_t>(cdiv(nLeafTiles, 16), 256);
@@ -2050,43 +2006,48 @@ static void kernel_event(vft_ctx *c) {   // three per sweep: before / between / 
     hipEventRecord(c->kev[c->kevUsed++], c->stream);
 }
 
-// makes sure the context owns `count` sets of sweep-result / selection buffers
+// padded node count of a slot's per-node arrays: slot 0's as the arena's (vft_create), the later slots' with four spare tiles
+static int64_t slot_nodes(const vft_ctx *c, int slot) { return (c->d.nTiles + (slot ? 4 : 0)) * VFT_TILE; }
+
+// makes sure the context owns `count` sets of sweep-result / selection buffers; every set is a group of its own
 static int ensure_slots(vft_ctx *c, int count) {
+    if (count > VFT_MAX_SLOTS) return fail(c, VFT_ERR_INVALID, "more than %d sweep slots", VFT_MAX_SLOTS);
+    c->slots.reserve(VFT_MAX_SLOTS);   // once: the owner keeps the addresses of a slot's members, so the slots must never move
     const size_t rs = c->rs;
-    const int64_t N = ((c->d.maxNodes + VFT_TILE - 1) / VFT_TILE + 4) * VFT_TILE;   // same padding as vft_create
     bool added = false;
     while ((int) c->slots.size() < count) {
-        vft_ctx::SweepSlotHost h;
-        void **reals[] = {&h.swDist, &h.swWeight, &h.swCrit};
-        for (void **p: reals) {
-            HIPCHK(c, hipMalloc(p, (size_t) N * rs));
-            HIPCHK(c, hipMemset(*p, 0, (size_t) N * rs));   // (as slot 0's arrays in vft_create)
+        const int slot = (int) c->slots.size();
+        const size_t N = (size_t) slot_nodes(c, slot);
+        // (the slot is in place before it is filled: after a failure the owner nulls its members where they are)
+        c->slots.emplace_back();
+        vft_ctx::SweepSlotHost &h = c->slots.back();
+        const int r = own_group(c, [&]() -> int {
+            void **reals[] = {&h.swDist, &h.swWeight, &h.swCrit};
+            for (void **p: reals) OWNCHK(own_dev(c, p, N * rs, 0));
+            const size_t nPartCap = (size_t) cdiv((int64_t) N, VFT_WG);
+            OWNCHK(own_dev(c, &h.partMin, nPartCap * 8));
+            OWNCHK(own_dev(c, &h.partMax, nPartCap * 8));
+            OWNCHK(own_dev(c, &h.sel, sizeof(SelectState), 0));
+            OWNCHK(own_dev(c, &h.slices, (size_t) VFT_NBINS * 4, 0));   // (the selection's histogram is zero between selections: k_select_rank's last workgroup leaves it so)
+            OWNCHK(own_dev(c, &h.candKey, (size_t) VFT_CAND_CAP * 8, 0));   // (never read before written since k_select_rank skips overflowed collections; zeroed all the same)
+            OWNCHK(own_dev(c, &h.candId, (size_t) VFT_CAND_CAP * 4, 0));
+            const size_t resB = sizeof(SelectHeader) + (size_t) c->hitsCap * sizeof(vft_hit_f64);
+            OWNCHK(own_dev(c, &h.dRes, resB));
+            OWNCHK(own_host(c, &h.hRes, &h.hResDev, resB, sizeof(SelectHeader)));
+            if (slot > 0 && c->cfg.n_codes == 4) {   // (slot 0's are the context's node-query buffers: vft_create points them there)
+                const size_t nPosPad = (size_t) c->d.nChunk * VFT_CHUNK;
+                OWNCHK(own_dev(c, &h.qW, nPosPad * rs));
+                OWNCHK(own_dev(c, &h.qF, nPosPad * 4 * rs));
+                OWNCHK(own_dev(c, &h.qC, nPosPad));
+                OWNCHK(own_dev(c, &h.qEnc, (size_t) c->d.nChunk * sizeof(uint4)));
+                OWNCHK(own_dev(c, &h.qTab, nPosPad * 5 * sizeof(double2)));
+            }
+            return VFT_OK;
+        });
+        if (r) {
+            c->slots.pop_back();
+            return r;
         }
-        const size_t nPartCap = (size_t) cdiv(N, VFT_WG);
-        HIPCHK(c, hipMalloc(&h.partMin, nPartCap * 8));
-        HIPCHK(c, hipMalloc(&h.partMax, nPartCap * 8));
-        HIPCHK(c, hipMalloc((void **) &h.sel, sizeof(SelectState)));
-        HIPCHK(c, hipMalloc((void **) &h.slices, (size_t) VFT_NBINS * 4));
-        HIPCHK(c, hipMemset(h.slices, 0, (size_t) VFT_NBINS * 4));
-        HIPCHK(c, hipMalloc((void **) &h.candKey, (size_t) VFT_CAND_CAP * 8));
-        HIPCHK(c, hipMalloc((void **) &h.candId, (size_t) VFT_CAND_CAP * 4));
-        HIPCHK(c, hipMemset(h.candKey, 0, (size_t) VFT_CAND_CAP * 8));   // (never read before written since k_select_rank skips overflowed collections; zeroed all the same)
-        HIPCHK(c, hipMemset(h.candId, 0, (size_t) VFT_CAND_CAP * 4));
-        HIPCHK(c, hipMemset(h.sel, 0, sizeof(SelectState)));
-        const size_t resB = sizeof(SelectHeader) + (size_t) c->hitsCap * sizeof(vft_hit_f64);
-        HIPCHK(c, hipMalloc((void **) &h.dRes, resB));
-        HIPCHK(c, hipHostMalloc((void **) &h.hRes, resB, hipHostMallocMapped));
-        HIPCHK(c, hipHostGetDevicePointer((void **) &h.hResDev, h.hRes, 0));
-        memset(h.hRes, 0, sizeof(SelectHeader));
-        if (c->cfg.n_codes == 4 && !c->slots.empty()) {   // (slot 0 is made by vft_create and uses the context's staging)
-            const size_t nPosPad = (size_t) c->d.nChunk * VFT_CHUNK;
-            HIPCHK(c, hipMalloc(&h.qW, nPosPad * rs));
-            HIPCHK(c, hipMalloc(&h.qF, nPosPad * 4 * rs));
-            HIPCHK(c, hipMalloc((void **) &h.qC, nPosPad));
-            HIPCHK(c, hipMalloc((void **) &h.qEnc, (size_t) c->d.nChunk * sizeof(uint4)));
-            HIPCHK(c, hipMalloc((void **) &h.qTab, nPosPad * 5 * sizeof(double2)));
-        }
-        c->slots.push_back(h);
         added = true;
     }
     // The hipMemsets of the new slots run on the NULL stream; the context's stream is non-blocking, so nothing orders them before the
@@ -2213,7 +2174,6 @@ static int sweep_one(vft_ctx *c, int slot, int64_t query, int64_t nActive, int64
     const int64_t span = hi > lo ? hi - lo : 0;
     const bool ntPath = c->cfg.n_codes == 4 && !c->hasDm;
     const unsigned grid = ntPath ? sweep_nt_grid(c, s, !s.queryIsLeaf) : cdiv(span > 0 ? span : 1, VFT_WG);
-    c->nPart = (int) grid;
     c->slots[(size_t) slot].nPart = (int) grid;
     const int64_t nPosPad = (int64_t) c->d.nChunk * VFT_CHUNK;
     if (c->cfg.n_codes == 4 && !c->hasDm) {
@@ -2236,11 +2196,9 @@ static int sweep_one(vft_ctx *c, int slot, int64_t query, int64_t nActive, int64
         kernel_event(c);
         if (c->cfg.n_codes == 20 && c->hasDm && c->aaLds && span > 0) {
             const unsigned g = c->cfg.precision == 4 ? launch_sweep_aa<float, MODE_CRIT>(c, s, 0, slot) : launch_sweep_aa<double, MODE_CRIT>(c, s, 0, slot);
-            c->nPart = (int) g;
             c->slots[(size_t) slot].nPart = (int) g;
         } else if (span <= 32768) {
             const unsigned wgrid = (unsigned) std::min<int64_t>(cdiv(span > 0 ? span : 1, c->pwWaves), 256 * 16);
-            c->nPart = (int) wgrid;
             c->slots[(size_t) slot].nPart = (int) wgrid;
             VFT_DISPATCH(c, (launch((k_sweep_wave<REAL, NC>), dim3(wgrid), dim3(64 * c->pwWaves), pw_lds_bytes(c), c->stream,
                                     arena<REAL>(c), s, sweepout<REAL>(c, slot))));
@@ -2276,7 +2234,6 @@ static int sweep_group(vft_ctx *c, bool leafSeeds, const int *slotOf, const int6
         c->slots[(size_t) slotOf[q]].nPart = (int) grid;
     }
     M.mq = (const REAL *) mq;
-    c->nPart = (int) grid;
     kernel_event(c);
     if (grid && leafSeeds) launch((k_sweep_nt_leafq_multi<REAL, S>), dim3(grid), dim3(VFT_WG), 0, c->stream, arena<REAL>(c), M, s);
     // profile seeds: heavy and table workgroups alike take all S seeds
@@ -2296,7 +2253,10 @@ static bool mixed_sweep_fits(vft_ctx *c) {
     s.hi = c->shardHi < c->maxnode ? c->shardHi : c->maxnode;
     const unsigned grid = sweep_nt_grid(c, s, true);
     if (!s.nLeafWG || grid == (unsigned) s.nLeafWG || s.hi <= s.leafEnd) return false;
-    const int64_t N = ((c->d.maxNodes + VFT_TILE - 1) / VFT_TILE + 4) * VFT_TILE;   // (ensure_slots)
+    // Single precision only (the caller's rule too), and that is what lets the bound be the later slots': a buffer has 8 bytes per
+    // partial, so slot 0's, one entry shorter, holds twice as many floats as the later slots' bound allows.
+    if (c->rs != 4) return false;
+    const int64_t N = slot_nodes(c, 1);
     return (int64_t) cdiv(s.leafEnd - s.lo, VFT_WG) + (int64_t) (grid - (unsigned) s.nLeafWG) <= (int64_t) cdiv(N, VFT_WG);
 }
 
@@ -2331,7 +2291,6 @@ static int sweep_mixed(vft_ctx *c, const int *leafPos, const int *profPos, const
     }
     a.M.L.mq = nullptr;
     a.M.P.mq = (const REAL *) mq;
-    c->nPart = (int) gridP;
     kernel_event(c);
     launch((k_sweep_nt_mixed_multi<REAL, S, S>), dim3((unsigned) (a.nInt + a.nLeafHeavy + s.nLeafWG)), dim3(VFT_WG), 0, c->stream, a);
     kernel_event(c);
@@ -2341,7 +2300,11 @@ static int sweep_mixed(vft_ctx *c, const int *leafPos, const int *profPos, const
     return VFT_OK;
 }
 
+// the calls that read slot 0 on a context whose creation failed before it had one
+static int no_slot(vft_ctx *c) { return fail(c, VFT_ERR_STATE, "the context has no sweep buffers (vft_create failed)"); }
+
 static int sweep_args_ok(vft_ctx *c, int64_t query, int64_t nActive, int32_t k) {
+    if (c->slots.empty()) return no_slot(c);
     if (!c->leavesUp) return fail(c, VFT_ERR_STATE, "vft_sweep before vft_upload_leaves");
     if (query < 0 || query >= c->maxnode || nActive < 3 || k < 0 || k > c->hitsCap)
         return fail(c, VFT_ERR_INVALID, "vft_sweep: bad arguments (query %lld, nActive %lld, k %d)", (long long) query,
@@ -2363,9 +2326,10 @@ extern "C" int vft_sweep(vft_ctx *c, int64_t query, int64_t nActive, int64_t nDi
     else r = run_select<double, vft_hit_f64>(c, 1, &query, lo, hi, k);
     if (r) return r;
     const size_t hb = (size_t) k * (c->cfg.precision == 4 ? sizeof(vft_hit_f32) : sizeof(vft_hit_f64));
-    if (dHitsOut) HIPCHK(c, hipMemcpyAsync(dHitsOut, c->dRes + sizeof(SelectHeader), hb, hipMemcpyDeviceToDevice, c->stream));
-    if (hits) memcpy(hits, c->hRes + sizeof(SelectHeader), hb);
-    if (bestJ) *bestJ = (int64_t) ((const SelectHeader *) c->hRes)->bestJ;
+    const vft_ctx::SweepSlotHost &h = c->slots[0];
+    if (dHitsOut) HIPCHK(c, hipMemcpyAsync(dHitsOut, h.dRes + sizeof(SelectHeader), hb, hipMemcpyDeviceToDevice, c->stream));
+    if (hits) memcpy(hits, h.hRes + sizeof(SelectHeader), hb);
+    if (bestJ) *bestJ = (int64_t) ((const SelectHeader *) h.hRes)->bestJ;
     return VFT_OK;
 }
 
@@ -2382,7 +2346,7 @@ struct SeedGroup {
 
 extern "C" int vft_sweep_batch(vft_ctx *c, int32_t nSeeds, const int64_t *queries, int64_t nActive, int64_t nDiffAllow,
                                double totdiam, int32_t k, void *hits, void *dHitsOut, int64_t *bestJ) {
-    if (!c || !queries || nSeeds < 1 || nSeeds > 64 || k < 1) return VFT_ERR_INVALID;
+    if (!c || !queries || nSeeds < 1 || nSeeds > VFT_MAX_SLOTS || k < 1) return VFT_ERR_INVALID;
     if (bestJ && k < 2) return fail(c, VFT_ERR_INVALID, "vft_sweep_batch: best_j needs k >= 2");
     for (int s = 0; s < nSeeds; s++)
         if (int r = sweep_args_ok(c, queries[s], nActive, k)) return r;
@@ -2418,7 +2382,7 @@ extern "C" int vft_sweep_batch(vft_ctx *c, int32_t nSeeds, const int64_t *querie
     const int64_t nPosPad = (int64_t) c->d.nChunk * VFT_CHUNK;
     const size_t mqGroupBytes = (size_t) nPosPad * VFT_MQ_STRIDE(4) * c->rs;
     if (!groups.empty() && !c->mqBuf) {   // (32 groups: the profile seeds of the largest batch, two per group)
-        HIPCHK(c, hipMalloc(&c->mqBuf, 32 * mqGroupBytes));
+        OWNCHK(own_dev(c, &c->mqBuf, 32 * mqGroupBytes));
         c->mqGroupBytes = mqGroupBytes;
     }
     if (staged) {
@@ -2524,20 +2488,20 @@ static int merge_hits_impl(vft_ctx *c, const void *dAll, int32_t nLists, int32_t
     HIT *dHits, *hHitsDev;
     const char *hHost;
     if (nSeeds == 1) {
-        dHits = (HIT *) (c->dRes + sizeof(SelectHeader));
-        hHitsDev = (HIT *) (c->hResDev + sizeof(SelectHeader));
-        hHost = c->hRes + sizeof(SelectHeader);
+        dHits = (HIT *) (c->slots[0].dRes + sizeof(SelectHeader));
+        hHitsDev = (HIT *) (c->slots[0].hResDev + sizeof(SelectHeader));
+        hHost = c->slots[0].hRes + sizeof(SelectHeader);
     } else {
         const size_t need = total * sizeof(vft_hit_f64);
         if (need > c->mergeBytes) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->dMerge) hipFree(c->dMerge);
-            if (c->hMerge) hipHostFree(c->hMerge);
-            c->dMerge = c->hMerge = c->hMergeDev = nullptr;
+            c->own.release(&c->dMerge);
+            c->own.release(&c->hMerge);
             c->mergeBytes = 0;
-            HIPCHK(c, hipMalloc((void **) &c->dMerge, need));
-            HIPCHK(c, hipHostMalloc((void **) &c->hMerge, need, hipHostMallocMapped));
-            HIPCHK(c, hipHostGetDevicePointer((void **) &c->hMergeDev, c->hMerge, 0));
+            OWNCHK(own_group(c, [&]() -> int {
+                OWNCHK(own_dev(c, &c->dMerge, need));
+                return own_host(c, &c->hMerge, &c->hMergeDev, need, 0);
+            }));
             c->mergeBytes = need;
         }
         dHits = (HIT *) c->dMerge;
@@ -2558,6 +2522,7 @@ static int merge_hits_impl(vft_ctx *c, const void *dAll, int32_t nLists, int32_t
 
 extern "C" int vft_merge_hits(vft_ctx *c, const void *dAll, int32_t nLists, int32_t k, void *hits, void *dOut) {
     if (!c || !dAll || nLists < 1 || k < 1 || k > c->hitsCap) return fail(c, VFT_ERR_INVALID, "vft_merge_hits: bad arguments");
+    if (c->slots.empty()) return no_slot(c);
     if (c->cfg.precision == 4) return merge_hits_impl<float, vft_hit_f32>(c, dAll, nLists, 1, k, hits, dOut);
     return merge_hits_impl<double, vft_hit_f64>(c, dAll, nLists, 1, k, hits, dOut);
 }
@@ -2572,7 +2537,8 @@ extern "C" int vft_merge_hits_batch(vft_ctx *c, const void *dAll, int32_t nLists
 
 extern "C" int vft_sweep_info(vft_ctx *c, int64_t info[2]) {
     if (!c || !info) return VFT_ERR_INVALID;
-    const SelectHeader *h = (const SelectHeader *) c->hRes;
+    if (c->slots.empty()) return no_slot(c);
+    const SelectHeader *h = (const SelectHeader *) c->slots[0].hRes;
     info[0] = h->nCand;
     info[1] = h->shift;
     return VFT_OK;
@@ -2590,10 +2556,11 @@ extern "C" int vft_sweep_batch_info(vft_ctx *c, int32_t slot, int64_t info[2]) {
 extern "C" int vft_sweep_results(vft_ctx *c, int64_t first, int64_t count, void *dist, void *weight, void *crit) {
     if (!c) return VFT_ERR_INVALID;
     if (int r = range_ok(c, first, count)) return r;
+    if (c->slots.empty()) return no_slot(c);
     const size_t rs = c->rs;
-    if (dist) HIPCHK(c, hipMemcpyAsync(dist, (char *) c->swDist + first * rs, count * rs, hipMemcpyDeviceToHost, c->stream));
-    if (weight) HIPCHK(c, hipMemcpyAsync(weight, (char *) c->swWeight + first * rs, count * rs, hipMemcpyDeviceToHost, c->stream));
-    if (crit) HIPCHK(c, hipMemcpyAsync(crit, (char *) c->swCrit + first * rs, count * rs, hipMemcpyDeviceToHost, c->stream));
+    if (dist) HIPCHK(c, hipMemcpyAsync(dist, (char *) c->slots[0].swDist + first * rs, count * rs, hipMemcpyDeviceToHost, c->stream));
+    if (weight) HIPCHK(c, hipMemcpyAsync(weight, (char *) c->slots[0].swWeight + first * rs, count * rs, hipMemcpyDeviceToHost, c->stream));
+    if (crit) HIPCHK(c, hipMemcpyAsync(crit, (char *) c->slots[0].swCrit + first * rs, count * rs, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return VFT_OK;
 }
@@ -2687,8 +2654,7 @@ static int pair_distances(vft_ctx *c, int64_t n, const int64_t *pi, const int64_
     //  whole grid is resident at once, whatever order the dispatcher picks)
     bool fusedRefresh = small && nStale > 0 && n <= 2048 && n + nStale <= c->fusedLimit && !c->noFusedRefresh;
     if (fusedRefresh && !c->refDone) {
-        HIPCHK(c, hipMalloc((void **) &c->refDone, 4096 * sizeof(unsigned int)));
-        HIPCHK(c, hipMemsetAsync(c->refDone, 0, 4096 * sizeof(unsigned int), c->stream));
+        OWNCHK(own_dev(c, &c->refDone, 4096 * sizeof(unsigned int), 0, ON_STREAM));
     }
     char *hBase = nullptr, *dBase = nullptr;
     if (small) {
@@ -3003,13 +2969,12 @@ extern "C" int vft_seq_matrix_rows(vft_ctx *c, int64_t r0, int64_t r1, int32_t l
 extern "C" int vft_exhaustive_destroy(vft_ctx *c) {
     if (!c) return VFT_ERR_INVALID;
     if (c->exM) (void) hipStreamSynchronize(c->stream);
-    void *dev[] = {c->exM, c->exSlotOut, c->exPart, c->exNodeOf, c->exSlotNode, c->exStale};
-    for (void *p: dev)
-        if (p) hipFree(p);
-    c->exM = c->exSlotOut = c->exPart = nullptr;
-    c->exNodeOf = nullptr;
-    c->exSlotNode = nullptr;
-    c->exStale = nullptr;
+    c->own.release(&c->exM);   // (the group of vft_exhaustive_create, which exists as a whole or not at all)
+    c->own.release(&c->exSlotOut);
+    c->own.release(&c->exPart);
+    c->own.release(&c->exNodeOf);
+    c->own.release(&c->exSlotNode);
+    c->own.release(&c->exStale);
     c->exLd = c->exLive = 0;
     return VFT_OK;
 }
@@ -3019,24 +2984,19 @@ extern "C" int vft_exhaustive_create(vft_ctx *c) {
     (void) vft_exhaustive_destroy(c);
     const int64_t S = c->d.nSeqs, ld = (S + 63) & ~(int64_t) 63;
     const size_t bytes = (size_t) S * (size_t) ld * c->rs;
-    if (hipMalloc(&c->exM, bytes) != hipSuccess) {
-        c->exM = nullptr;
-        (void) hipGetLastError();
-        return fail(c, VFT_ERR_HIP, "vft_exhaustive_create: no device memory for the %lld x %lld distance matrix (%zu bytes)", (long long) S,
-                    (long long) ld, bytes);
-    }
-    c->exLd = ld;
     const size_t keyBytes = c->rs == 4 ? sizeof(ExKey<float>) : sizeof(ExKey<double>);
-    if (hipMalloc(&c->exSlotOut, (size_t) ld * c->rs) != hipSuccess || hipMalloc(&c->exPart, VFT_EX_MAX_PARTS * keyBytes) != hipSuccess ||
-        hipMalloc((void **) &c->exNodeOf, (size_t) ld * sizeof(int64_t)) != hipSuccess ||
-        hipMalloc((void **) &c->exSlotNode, (size_t) ld * sizeof(int32_t)) != hipSuccess ||
-        hipMalloc((void **) &c->exStale, sizeof(unsigned int)) != hipSuccess) {
-        (void) hipGetLastError();
-        (void) vft_exhaustive_destroy(c);
-        return fail(c, VFT_ERR_HIP, "vft_exhaustive_create: no device memory for the slot arrays of %lld sequences", (long long) S);
-    }
-    HIPCHK(c, hipMemsetAsync(c->exStale, 0, sizeof(unsigned int), c->stream));
-    return VFT_OK;
+    return own_group(c, [&]() -> int {
+        if (own_dev(c, &c->exM, bytes))
+            return fail(c, VFT_ERR_HIP, "vft_exhaustive_create: no device memory for the %lld x %lld distance matrix (%zu bytes)", (long long) S,
+                        (long long) ld, bytes);
+        if (own_dev(c, &c->exSlotOut, (size_t) ld * c->rs) || own_dev(c, &c->exPart, VFT_EX_MAX_PARTS * keyBytes) ||
+            own_dev(c, &c->exNodeOf, (size_t) ld * sizeof(int64_t)) || own_dev(c, &c->exSlotNode, (size_t) ld * sizeof(int32_t)) ||
+            own_dev(c, &c->exStale, sizeof(unsigned int)))
+            return fail(c, VFT_ERR_HIP, "vft_exhaustive_create: no device memory for the slot arrays of %lld sequences", (long long) S);
+        HIPCHK(c, hipMemsetAsync(c->exStale, 0, sizeof(unsigned int), c->stream));
+        c->exLd = ld;
+        return VFT_OK;
+    });
 }
 
 extern "C" int vft_exhaustive_fill(vft_ctx *c) {
@@ -3177,24 +3137,23 @@ extern "C" int vft_tophits_create(vft_ctx *c, int32_t m, int64_t nLists) {
     c->thM = m;
     c->thCap = 2 * m + 64;
     c->thLists = nLists;
-    HIPCHK(c, hipMalloc(&c->thHits, (size_t) nLists * (size_t) m * hitB));
-    HIPCHK(c, hipMalloc((void **) &c->thLen, (size_t) nLists * 4));
-    HIPCHK(c, hipMemsetAsync(c->thLen, 0, (size_t) nLists * 4, c->stream));
-    HIPCHK(c, hipMalloc((void **) &c->thStJ, (size_t) c->thCap * 4));
-    HIPCHK(c, hipMalloc(&c->thStD, (size_t) c->thCap * c->rs));
-    HIPCHK(c, hipMalloc(&c->thStC, (size_t) c->thCap * c->rs));
-    HIPCHK(c, hipMalloc((void **) &c->thMark, (size_t) c->d.maxNodes * 4));
-    HIPCHK(c, hipMemsetAsync(c->thMark, 0, (size_t) c->d.maxNodes * 4, c->stream));
-    HIPCHK(c, hipMalloc((void **) &c->thSorted, (size_t) (c->thCap + 1) * 4));
-    HIPCHK(c, hipMalloc((void **) &c->thDone, 65 * 4));
-    HIPCHK(c, hipMemsetAsync(c->thDone, 0, 65 * 4, c->stream));
     c->thTag = 0;
-    if (c->thLds > (48u << 10))
-        VFT_DISPATCH(c, {
-            HIPCHK(c, hipFuncSetAttribute((const void *) k_th_best<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) c->thLds));
-            HIPCHK(c, hipFuncSetAttribute((const void *) k_th_join<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) c->thLds));
-        });
-    return VFT_OK;
+    return own_group(c, [&]() -> int {   // (after a failure there are no lists, and a later call may make them)
+        OWNCHK(own_dev(c, &c->thHits, (size_t) nLists * (size_t) m * hitB));
+        OWNCHK(own_dev(c, &c->thLen, (size_t) nLists * 4, 0, ON_STREAM));
+        OWNCHK(own_dev(c, &c->thStJ, (size_t) c->thCap * 4));
+        OWNCHK(own_dev(c, &c->thStD, (size_t) c->thCap * c->rs));
+        OWNCHK(own_dev(c, &c->thStC, (size_t) c->thCap * c->rs));
+        OWNCHK(own_dev(c, &c->thMark, (size_t) c->d.maxNodes * 4, 0, ON_STREAM));
+        OWNCHK(own_dev(c, &c->thSorted, (size_t) (c->thCap + 1) * 4));
+        OWNCHK(own_dev(c, &c->thDone, 65 * 4, 0, ON_STREAM));
+        if (c->thLds > (48u << 10))
+            VFT_DISPATCH(c, {
+                HIPCHK(c, hipFuncSetAttribute((const void *) k_th_best<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) c->thLds));
+                HIPCHK(c, hipFuncSetAttribute((const void *) k_th_join<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) c->thLds));
+            });
+        return VFT_OK;
+    });
 }
 
 extern "C" int vft_tophits_upload(vft_ctx *c, int64_t count, const int64_t *nodes, const int32_t *lens, const void *packed) {
@@ -3479,7 +3438,7 @@ static __global__ void k_copy_i32(int32_t *dst, const int32_t *src, int64_t n) {
     if (t < n) dst[t] = src[t];
 }
 
-static int nj_engine_create_impl(vft_ctx *c, const vft_nj_engine_config *cfg) {
+extern "C" int vft_nj_engine_create(vft_ctx *c, const vft_nj_engine_config *cfg) {
     if (!c || !cfg || cfg->m < 1 || cfg->n_top < 1) return VFT_ERR_INVALID;
     if (!c->thHits || cfg->m != c->thM) return fail(c, VFT_ERR_STATE, "vft_nj_engine_create: vft_tophits_create(m) first");
     if (c->njState) return fail(c, VFT_ERR_STATE, "vft_nj_engine_create: the engine exists already");
@@ -3500,86 +3459,47 @@ static int nj_engine_create_impl(vft_ctx *c, const vft_nj_engine_config *cfg) {
     c->njTailThreads = std::max(cfg->n_top, P) <= VFT_NJ_BATCH * VFT_NJ_TAIL && !c->wideGlue ? VFT_NJ_TAIL : 1024;
     if (std::max(cfg->n_top, P) > VFT_NJ_BATCH * 1024) return fail(c, VFT_ERR_STATE, "vft_nj_engine_create: lists too long for the glue kernel");
     if (int r = ensure_ml_rows(c)) return r;
-    if (!c->pendBase) {
-        const CommitPlan plan = commit_plan(c, VFT_PEND_MAX);
-        HIPCHK(c, hipMalloc((void **) &c->pendBase, plan.totalB + 512));
-        HIPCHK(c, hipMalloc((void **) &c->pendIdsDev, VFT_PEND_MAX * sizeof(int64_t)));
-    }
+    if (int r = ensure_pend(c)) return r;
     const size_t nodes = (size_t) c->d.maxNodes, joins = (size_t) c->d.nSeqs;
-    HIPCHK(c, hipMalloc(&c->njState, stB));
-    HIPCHK(c, hipMemsetAsync(c->njState, 0, stB, c->stream));
-    HIPCHK(c, hipMalloc((void **) &c->njVisJ, nodes * 4));
-    HIPCHK(c, hipMemsetAsync(c->njVisJ, 0xFF, nodes * 4, c->stream));
-    HIPCHK(c, hipMalloc(&c->njVisD, nodes * rs));
-    HIPCHK(c, hipMemsetAsync(c->njVisD, 0, nodes * rs, c->stream));
-    HIPCHK(c, hipMalloc((void **) &c->njTop, (size_t) cfg->n_top * 4));
-    HIPCHK(c, hipMemsetAsync(c->njTop, 0xFF, (size_t) cfg->n_top * 4, c->stream));
-    HIPCHK(c, hipMalloc((void **) &c->njAge, nodes * 4));
-    HIPCHK(c, hipMemsetAsync(c->njAge, 0, nodes * 4, c->stream));
-    HIPCHK(c, hipMalloc((void **) &c->njLogDev, joins * sizeof(NjJoinRec)));
-    HIPCHK(c, hipMalloc((void **) &c->njClaim, nodes * 4));
-    HIPCHK(c, hipMemsetAsync(c->njClaim, 0, nodes * 4, c->stream));
-    HIPCHK(c, hipMalloc((void **) &c->njLogNode, (size_t) (cfg->m + 64) * 4));
-    HIPCHK(c, hipMalloc((void **) &c->njLogStamp, (size_t) (cfg->m + 64) * 4));
-    HIPCHK(c, hipMalloc(&c->njLogOut, (size_t) (cfg->m + 64) * rs));
     c->njTopPad = (cfg->n_top + 63) & ~63;
     c->njCapPad = (c->thCap + 63) & ~63;
-    HIPCHK(c, hipMalloc((void **) &c->njSlotI, (size_t) 6 * c->njTopPad * 4));
-    HIPCHK(c, hipMalloc(&c->njSlotR, (size_t) 3 * c->njTopPad * rs));
-    HIPCHK(c, hipMalloc((void **) &c->njCandI, (size_t) 5 * c->njCapPad * 4));
-    HIPCHK(c, hipMalloc(&c->njCandR, (size_t) 5 * c->njCapPad * rs));
-    HIPCHK(c, hipMemsetAsync(c->njSlotI, 0, (size_t) 6 * c->njTopPad * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->njSlotR, 0, (size_t) 3 * c->njTopPad * rs, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->njCandI, 0, (size_t) 5 * c->njCapPad * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->njCandR, 0, (size_t) 5 * c->njCapPad * rs, c->stream));
-    HIPCHK(c, hipHostMalloc((void **) &c->njLogHost, joins * sizeof(NjJoinRec), hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer((void **) &c->njLogHostDev, c->njLogHost, 0));
-    memset(c->njLogHost, 0xFF, joins * sizeof(NjJoinRec));   // an unwritten record fails vft_nj_engine_adopt's check (newnode = -1)
-    HIPCHK(c, hipHostMalloc((void **) &c->njStatusHost, 64, hipHostMallocMapped));
-    HIPCHK(c, hipHostGetDevicePointer((void **) &c->njStatusDev, c->njStatusHost, 0));
-    memset(c->njStatusHost, 0, 64);
-    VFT_DISPATCH(c, {
-        if (c->njTailLds > (48u << 10)) {
-            HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_glue_scan<REAL, NC, VFT_NJ_TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) c->njTailLds));
-            HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_glue_scan<REAL, NC, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) c->njTailLds));
-        }
-        if ((size_t) P * sizeof(ThKey) > (48u << 10))
-            HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_merge_rank<REAL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ((size_t) P * sizeof(ThKey))));
-        if (2 * pairLds > (48u << 10)) {
-            HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_glue_best<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pairLds));
-            HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_best_pairs<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pairLds));
-            HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_best_pairs2<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pairLds));
-            HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_glue_join<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (2 * pairLds)));
-            HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_refresh_new<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pairLds));
-            HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_merge_pairs<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pairLds));
-        }
+    // the engine's own buffers (not the ML rows and the pending stash above, which other calls share): all of them or no engine
+    return own_group(c, [&]() -> int {
+        OWNCHK(own_dev(c, &c->njState, stB, 0, ON_STREAM));
+        OWNCHK(own_dev(c, &c->njVisJ, nodes * 4, 0xFF, ON_STREAM));
+        OWNCHK(own_dev(c, &c->njVisD, nodes * rs, 0, ON_STREAM));
+        OWNCHK(own_dev(c, &c->njTop, (size_t) cfg->n_top * 4, 0xFF, ON_STREAM));
+        OWNCHK(own_dev(c, &c->njAge, nodes * 4, 0, ON_STREAM));
+        OWNCHK(own_dev(c, &c->njLogDev, joins * sizeof(NjJoinRec)));
+        OWNCHK(own_dev(c, &c->njClaim, nodes * 4, 0, ON_STREAM));
+        OWNCHK(own_dev(c, &c->njLogNode, (size_t) (cfg->m + 64) * 4));
+        OWNCHK(own_dev(c, &c->njLogStamp, (size_t) (cfg->m + 64) * 4));
+        OWNCHK(own_dev(c, &c->njLogOut, (size_t) (cfg->m + 64) * rs));
+        OWNCHK(own_dev(c, &c->njSlotI, (size_t) 6 * c->njTopPad * 4, 0, ON_STREAM));
+        OWNCHK(own_dev(c, &c->njSlotR, (size_t) 3 * c->njTopPad * rs, 0, ON_STREAM));
+        OWNCHK(own_dev(c, &c->njCandI, (size_t) 5 * c->njCapPad * 4, 0, ON_STREAM));
+        OWNCHK(own_dev(c, &c->njCandR, (size_t) 5 * c->njCapPad * rs, 0, ON_STREAM));
+        OWNCHK(own_host(c, &c->njLogHost, &c->njLogHostDev, joins * sizeof(NjJoinRec), 0));
+        memset(c->njLogHost, 0xFF, joins * sizeof(NjJoinRec));   // an unwritten record fails vft_nj_engine_adopt's check (newnode = -1)
+        OWNCHK(own_host(c, &c->njStatusHost, &c->njStatusDev, 64, 64));
+        VFT_DISPATCH(c, {
+            if (c->njTailLds > (48u << 10)) {
+                HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_glue_scan<REAL, NC, VFT_NJ_TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) c->njTailLds));
+                HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_glue_scan<REAL, NC, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) c->njTailLds));
+            }
+            if ((size_t) P * sizeof(ThKey) > (48u << 10))
+                HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_merge_rank<REAL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ((size_t) P * sizeof(ThKey))));
+            if (2 * pairLds > (48u << 10)) {
+                HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_glue_best<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pairLds));
+                HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_best_pairs<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pairLds));
+                HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_best_pairs2<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pairLds));
+                HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_glue_join<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) (2 * pairLds)));
+                HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_refresh_new<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pairLds));
+                HIPCHK(c, hipFuncSetAttribute((const void *) k_nj_merge_pairs<REAL, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) pairLds));
+            }
+        });
+        return VFT_OK;
     });
-    return VFT_OK;
-}
-
-// every buffer of the engine, released: after a failed creation the context must not look as if it had one
-static void nj_engine_free(vft_ctx *c) {
-    void **dev[] = {&c->njState, &c->njVisD, (void **) &c->njVisJ, (void **) &c->njTop, (void **) &c->njAge, (void **) &c->njLogDev, (void **) &c->njClaim,
-                    (void **) &c->njLogNode, (void **) &c->njLogStamp, &c->njLogOut, (void **) &c->njSlotI, &c->njSlotR, (void **) &c->njCandI, &c->njCandR};
-    for (void **p: dev)
-        if (*p) {
-            hipFree(*p);
-            *p = nullptr;
-        }
-    if (c->njLogHost) hipHostFree(c->njLogHost);
-    if (c->njStatusHost) hipHostFree(c->njStatusHost);
-    c->njLogHost = c->njLogHostDev = nullptr;
-    c->njStatusHost = c->njStatusDev = nullptr;
-}
-
-extern "C" int vft_nj_engine_create(vft_ctx *c, const vft_nj_engine_config *cfg) {
-    const bool had = c && c->njState;   // ("the engine exists already" must leave that engine alone)
-    const int r = nj_engine_create_impl(c, cfg);
-    if (r != VFT_OK && c && !had && c->njState) {
-        hipStreamSynchronize(c->stream);
-        nj_engine_free(c);
-    }
-    return r;
 }
 
 #define NJ_ENGINE_OK(c) do { if (!(c)) return VFT_ERR_INVALID; if (!(c)->njState) return fail((c), VFT_ERR_STATE, "no join engine (vft_nj_engine_create)"); } while (0)
@@ -3718,7 +3638,6 @@ extern "C" int vft_nj_engine_reset_candidates(vft_ctx *c, int64_t nActive, doubl
     }
     // 2. criteria as a sweep-shaped result in slot 0, 3. the selection of the sweeps
     if (int r = ensure_slots(c, 1)) return r;
-    c->nPart = (int) grid;
     c->slots[0].nPart = (int) grid;
     if (c->rs == 4) launch((k_nj_reset_crit<float>), dim3(grid), dim3(VFT_WG), 0, c->stream, arena<float>(c), njengine<float>(c), sa, maxnode, sweepout<float>(c, 0), dCnt + 1);
     else launch((k_nj_reset_crit<double>), dim3(grid), dim3(VFT_WG), 0, c->stream, arena<double>(c), njengine<double>(c), sa, maxnode, sweepout<double>(c, 0), dCnt + 1);
@@ -3730,7 +3649,7 @@ extern "C" int vft_nj_engine_reset_candidates(vft_ctx *c, int64_t nActive, doubl
     else r = run_select<double, vft_hit_f64>(c, 1, &query, 0, maxnode, k);
     if (r) return r;
     *nVisible = (int64_t) ((volatile unsigned int *) h)[1];
-    memcpy(hits, c->hRes + sizeof(SelectHeader), (size_t) k * (c->cfg.precision == 4 ? sizeof(vft_hit_f32) : sizeof(vft_hit_f64)));
+    memcpy(hits, c->slots[0].hRes + sizeof(SelectHeader), (size_t) k * (c->cfg.precision == 4 ? sizeof(vft_hit_f32) : sizeof(vft_hit_f64)));
     return VFT_OK;
 }
 
@@ -4004,9 +3923,7 @@ extern "C" int vft_posterior_profiles(vft_ctx *c, int64_t n, const int64_t *out,
 // in place, so a whole traversal is queued without a host round trip.
 static int ensure_blen(vft_ctx *c) {
     if (c->blen) return VFT_OK;
-    HIPCHK(c, hipMalloc(&c->blen, (size_t) c->d.maxNodes * c->rs));
-    HIPCHK(c, hipMemsetAsync(c->blen, 0, (size_t) c->d.maxNodes * c->rs, c->stream));
-    return VFT_OK;
+    return own_dev(c, &c->blen, (size_t) c->d.maxNodes * c->rs, 0, ON_STREAM);
 }
 
 extern "C" int vft_branch_lengths_set(vft_ctx *c, int64_t first, int64_t count, const void *values) {
@@ -4208,15 +4125,7 @@ static int ensure_ml_long_ws(vft_ctx *c, size_t nWG, int nRows, size_t *stride) 
     *stride = (vft_ml_long_ws_bytes(c->d.nPos, c->d.nCodes, c->rs, nRows) + 255) & ~(size_t) 255;
     const size_t bytes = nWG * *stride;
     if (bytes <= c->mlLongWsBytes) return VFT_OK;
-    if (c->mlLongWs) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(c->mlLongWs));
-        c->mlLongWs = nullptr;
-        c->mlLongWsBytes = 0;
-    }
-    HIPCHK(c, hipMalloc((void **) &c->mlLongWs, bytes));
-    c->mlLongWsBytes = bytes;
-    return VFT_OK;
+    return own_regrow(c, &c->mlLongWs, &c->mlLongWsBytes, bytes);
 }
 
 template <typename REAL, int NC>
@@ -4267,10 +4176,7 @@ extern "C" int vft_ml_optimize_splits(vft_ctx *c, int64_t n, const int64_t *ids,
                 return fail(c, VFT_ERR_INVALID, "vft_ml_optimize_splits: split %lld out of range", (long long) k);
     }
     if (int r = ensure_blen(c)) return r;
-    if (!c->mlEvals) {
-        HIPCHK(c, hipMalloc((void **) &c->mlEvals, sizeof(unsigned int)));
-        HIPCHK(c, hipMemsetAsync(c->mlEvals, 0, sizeof(unsigned int), c->stream));
-    }
+    if (!c->mlEvals) OWNCHK(own_dev(c, &c->mlEvals, sizeof(unsigned int), 0, ON_STREAM));
     if (int r = ensure_ml_rows(c)) return r;
     bool quad;
     const int cpt = mlopt_cpt(c, quad);
@@ -4340,10 +4246,7 @@ static int ml_quartet_nni(vft_ctx *c, int64_t n, const int64_t *ids, const int64
     if (!c->hasTm && c->d.nCodes != 4) return fail(c, VFT_ERR_STATE, "amino-acid likelihoods need vft_set_transition_matrix");
     if (int r = quartet_args_ok(c, n, ids, lenIdx, "vft_ml_quartet_nni")) return r;
     if (int r = ensure_blen(c)) return r;
-    if (!c->mlEvals) {
-        HIPCHK(c, hipMalloc((void **) &c->mlEvals, sizeof(unsigned int)));
-        HIPCHK(c, hipMemsetAsync(c->mlEvals, 0, sizeof(unsigned int), c->stream));
-    }
+    if (!c->mlEvals) OWNCHK(own_dev(c, &c->mlEvals, sizeof(unsigned int), 0, ON_STREAM));
     bool quad;
     const int cpt = mlopt_cpt(c, quad);
     const size_t idB = (size_t) n * 8, resB = (size_t) n * sizeof(QuartetNNIResult);
@@ -4407,10 +4310,7 @@ extern "C" int vft_ml_split_tests(vft_ctx *c, int64_t n, const int64_t *ids, con
     if (!c->hasTm && c->d.nCodes != 4) return fail(c, VFT_ERR_STATE, "amino-acid likelihoods need vft_set_transition_matrix");
     if (int r = quartet_args_ok(c, n, ids, lenIdx, "vft_ml_split_tests")) return r;
     if (int r = ensure_blen(c)) return r;
-    if (!c->mlEvals) {
-        HIPCHK(c, hipMalloc((void **) &c->mlEvals, sizeof(unsigned int)));
-        HIPCHK(c, hipMemsetAsync(c->mlEvals, 0, sizeof(unsigned int), c->stream));
-    }
+    if (!c->mlEvals) OWNCHK(own_dev(c, &c->mlEvals, sizeof(unsigned int), 0, ON_STREAM));
     const int64_t nPos = c->d.nPos;
     bool quad;
     const int cpt = mlopt_cpt(c, quad);
