@@ -125,7 +125,7 @@ typedef struct {
                                    joins), intree with slow (the NNI and SPR stages of a -slow run are not built), with a vft_comm of
                                    more than one rank, with fewer than 4 unique sequences, and every tree vft_read_tree refuses. */
     double pseudo_weight;       /* `-pseudo [W]` (Options::pseudoWeight, correctedPairDistances NJ.tcc:1460-1488; "recommended if the alignment
-                                   has sequences with little or no overlap"): 0 = off (the last member: a zero-initialised caller keeps
+                                   has sequences with little or no overlap"): 0 = off (a zero-initialised caller keeps
                                    everything above); W > 0 = every triplet / quartet of the minimum-evolution stages - the NNIs, every SPR
                                    chain step, updateBranchLengths - replaces its raw distances by
                                    (dist * weight + prior * W) / (weight + W), prior = the quartet's weighted mean distance (3.0 when
@@ -134,6 +134,28 @@ typedef struct {
                                    slow only the ME lengths do.  The SPR chains send no dual commands then (vft_nj_last_walk_dual
                                    reports 0 / 0).  Refused before anything reaches the device: a negative or non-finite weight, and
                                    W > 0 with a vft_comm of more than one rank (the lane exchange carries no weights). */
+    /* The thorough search (`-spr 4 -mlacc 2 -slownni` is the accuracy recipe of FastTree's documentation).  In each of the five members
+       below 0 means the reference's default: a zero-initialised caller keeps everything above.  A negative value is refused before
+       anything reaches the device, with a message that names the member.  threads composes with all five, as in the reference. */
+    int32_t ml_accuracy;        /* `-mlacc N` (Options::mlAccuracy, main.cpp:204): 0 / 1 = the default; N >= 2 = every quartet of an ML NNI
+                                   is optimised for N rounds instead of 2 (MLQuartetNNI, NJ.tcc:4893) and no alternative is ever dropped
+                                   (NJ.tcc:4957-4981), setMLGtr makes N rounds over the six rates (NJ.tcc:6462), and the SH-like supports
+                                   always optimise the better alternative a second time (testSplitsML, NJ.tcc:6934, :6940).  Read by
+                                   ml_nni, by gtr and by the SH-like supports (mllen included); without an ML stage it changes
+                                   nothing, as in the reference. */
+    int32_t slow_nni;           /* `-slownni` (Options::fastNNI = false): 1 = DoNNI marks no subtree as skippable (NJ.tcc:6049-6075) -
+                                   every internal node is visited in every round, in the minimum-evolution rounds (me_nni) and the
+                                   ML rounds (ml_nni) alike; with neither it changes nothing. */
+    int32_t nni_rounds;         /* `-nni N` (VeryFastTreeImpl.tcc:145): N > 0 = N minimum-evolution NNI rounds instead of
+                                   round(4 log2 n); the SPR rounds then sit behind every (N / (spr + 1))-th NNI round, all of them at
+                                   the end when that is 0 (VeryFastTreeImpl.tcc:187-204).  Read with me_nni only; `-nni 0` is
+                                   me_nni = 0 with spr = 0 (VeryFastTree.cpp:72). */
+    int32_t ml_nni_rounds;      /* `-mlnni N` (VeryFastTreeImpl.tcc:148): N > 0 = at most N ML NNI rounds instead of round(2 log2 n);
+                                   the NNI statistics are reset before round N - 1 (iMLnni == MLnniToDo - 2, VeryFastTreeImpl.tcc:345).
+                                   Read with ml_nni only; `-mlnni 0` is ml_nni = 0. */
+    int32_t spr_length;         /* `-sprlength N` (Options::maxSPRLength, default 10; findSPRSteps NJ.tcc:1808): N > 0 = the longest
+                                   chain of an SPR move.  Read with spr > 0 only.  More than 64 is refused: the chain buffers of
+                                   MLLengths::sprAttempt hold 64 steps. */
 } vft_nj_options;
 #define VFT_NJ_DEBUG_HOST_JOINS 1
 #define VFT_NJ_DEBUG_HOST_LISTS 2
@@ -231,6 +253,13 @@ int vft_nj_lane_share(int64_t n_items, int32_t world, int32_t rank, int64_t item
    test that runs it over gloo: out[0] = the rank that sums block `block` of `parts`, out[1] = the block's slot in that rank's share,
    out[2] = slots per share, out[3], out[4] = the block's entries [i0, i1) of an active list of n nodes */
 int vft_nj_out_profile_block(int32_t parts, int32_t world, int32_t block, int64_t n, int64_t *out);
+
+/* The rounds of the refinement stages of a run over n_seqs unique sequences (VeryFastTreeImpl.tcc:145-149, :187-204, :345), pure host
+   code - what the driver's loops read: nni_rounds / ml_nni_rounds as in vft_nj_options (0 = the defaults round(4 log2 n) / round(2 log2 n)),
+   spr = the number of SPR rounds.  out[0] = minimum-evolution NNI rounds, out[1] = ML NNI rounds, out[2] = the 0-based ML round behind
+   which the NNI statistics are reset (out[1] - 2: negative = never); spr_behind[cap] (may be NULL): per SPR round the number of NNI
+   rounds it runs behind - a multiple of out[0] / (spr + 1), or out[0] for the rounds left over at the end. */
+int vft_nj_round_plan(int64_t n_seqs, int32_t nni_rounds, int32_t ml_nni_rounds, int32_t spr, int64_t *out, int64_t *spr_behind, int64_t cap);
 
 /* out[3]: what `-gamma` (vft_nj_options.gamma) found for the last tree of this process - the Gamma(nCat) log-likelihood, the shape
    alpha, the factor every branch length was multiplied by (the reference's "Gamma(20) LogLk = .. alpha = .. rescaling lengths by ..") */

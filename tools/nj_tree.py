@@ -9,6 +9,7 @@ or - with -mllen - the tree of `VeryFastTree -nt -nome -mllen [-nocat | -cat N] 
     python tools/nj_tree.py in.fasta -full -threads 64 [-gamma] [-spr N] > tree.nwk   # the schedule of `VeryFastTree -threads 64`; -gamma; -spr N rounds
     python tools/nj_tree.py in.fasta -intree start.nwk [-mllen ... | -full ...] > tree.nwk   # `VeryFastTree -intree start.nwk ...`: no NJ phase
     python tools/nj_tree.py in.fasta [any mode above] -pseudo [W] > tree.nwk   # `VeryFastTree ... -pseudo [W]`: pseudocount distances
+    python tools/nj_tree.py in.fasta -full -spr 4 -mlacc 2 -slownni [-nni N] [-mlnni N] [-sprlength N] > tree.nwk   # the thorough search
     python tools/nj_tree.py -makematrix [-rawdist] [-aa] [-double] in.fasta > matrix.txt   # `VeryFastTree [-nt] [-rawdist] [-double-precision] -makematrix`
 
 Neighbour joining with top hits on the device (veryfasttree_amd/host/NJDriver.h), the root, minimum-evolution branch
@@ -30,6 +31,12 @@ error; not together with any tree option.
 -pseudo [W]: the reference's `-pseudo [weight]`, "recommended if the alignment has sequences with little or no overlap": the
 minimum-evolution stages (NNIs, SPR moves, ME branch lengths) estimate the distances of every triplet / quartet with pseudocounts of
 weight W (1.0 when no number follows; any W >= 0, 0 = off).  Not read by the NJ phase, the supports, the ML stage and -makematrix.
+-mlacc N, -slownni, -nni N, -mlnni N, -sprlength N: the reference's options of the same names, with -full (`-spr 4 -mlacc 2 -slownni` is
+the accuracy recipe of FastTree's documentation).  -mlacc N: every quartet of an ML NNI is optimised for N rounds and no alternative is
+dropped early, N rounds of the -gtr fit, the supports' second pass always (also with -mllen, for its supports and -gtr).  -slownni: no
+subtree is skipped in any NNI round.  -nni N / -mlnni N: N minimum-evolution / ML NNI rounds instead of round(4 log2 n) / round(2 log2 n);
+-nni 0 also means -spr 0, -mlnni 0 is -noml.  -sprlength N: SPR chains of at most N steps (default 10, at most 64).  Given without -full
+they end the program with a message.
 -boot N: N resamples instead of 1000 for the supports, local (default mode) and SH-like (-mllen, -full) alike, as the reference's
 -boot; -boot 0 is -nosupport.  Local supports take every alignment the NJ phase takes (10 240 columns).
 Sequence normalisation and uniquify follow Alignment.cpp:453-526 (U -> T, '.' -> '-', duplicates by sequence string in
@@ -106,6 +113,49 @@ def parse_pseudo(args):
     return weight, args
 
 
+THOROUGH_COUNTS = {"-mlacc": ("ml_accuracy", 1), "-nni": ("nni_rounds", 0), "-mlnni": ("ml_nni_rounds", 0), "-sprlength": ("spr_length", 1)}   # flag: (keyword, least N)
+
+
+def parse_thorough(args):
+    """`-mlacc N` (N >= 1), `-slownni`, `-nni N`, `-mlnni N` (N >= 0), `-sprlength N` (1 .. 64): returns (the keywords of nj_newick that
+    were asked for, args without these options).  A flag without its whole number, or with one out of range, ends the program."""
+    args, kw = list(args), {}
+    if "-slownni" in args:
+        args.remove("-slownni")
+        kw["slow_nni"] = True
+    for flag, (key, least) in THOROUGH_COUNTS.items():
+        if flag not in args:
+            continue
+        k = args.index(flag)
+        try:
+            kw[key] = int(args[k + 1])
+        except (IndexError, ValueError):
+            sys.exit("%s needs a whole number" % flag)
+        if kw[key] < least or (flag == "-sprlength" and kw[key] > 64):
+            sys.exit("%s needs a number %s, not %d" % (flag, "from 1 to 64 (the SPR chain buffers hold 64 steps)" if flag == "-sprlength" else ">= %d" % least, kw[key]))
+        del args[k:k + 2]
+    return kw, args
+
+
+def thorough_stages(kw, full, mllen):
+    """where the thorough-search options are valid: all of them with -full; -mlacc also with -mllen, whose SH-like supports and -gtr fit
+    read it (NJ.tcc:6934, :6462).  Returns the keywords for nj_newick - `-nni 0` as me_nni=False with spr=0 (VeryFastTree.cpp:72),
+    `-mlnni 0` as ml_nni=0 - or ends the program: an option that cannot take effect is not ignored."""
+    names = {"slow_nni": "-slownni"}
+    names.update({key: flag for flag, (key, _) in THOROUGH_COUNTS.items()})
+    for key in kw:
+        if not (full or (key == "ml_accuracy" and mllen)):
+            sys.exit("%s needs -full%s: without it the stage the option belongs to does not run" % (names[key], " or -mllen" if key == "ml_accuracy" else ""))
+    out = dict(kw)
+    if out.get("nni_rounds") == 0:
+        del out["nni_rounds"]
+        out.update(me_nni=False, spr=0)
+    if out.get("ml_nni_rounds") == 0:
+        del out["ml_nni_rounds"]
+        out["ml_nni"] = 0
+    return out
+
+
 MAKEMATRIX_FLAGS = ("-makematrix", "-rawdist", "-aa", "-double")
 
 
@@ -134,6 +184,7 @@ def main():
     if "-makematrix" in args:
         return main_makematrix(args)
     pseudo, args = parse_pseudo(args)
+    thorough, args = parse_thorough(args)
     if not args or args[0].startswith("-"):
         sys.exit(__doc__)
     fastest, double, nj_len = "-fastest" in args, "-double" in args, "-nj-lengths" in args
@@ -165,6 +216,8 @@ def main():
         extra["threads"] = int(args[args.index("-threads") + 1])
     if "-gamma" in args and extra:
         extra["gamma"] = True
+    label = "Round" if extra else "Length"   # of the TreeLogLk lines: by the stages that run, whatever -mlacc adds to a -mllen run
+    extra.update(thorough_stages(thorough, "-full" in args, mllen != 0))   # (behind -spr: `-nni 0` switches the SPR rounds off)
     names, seqs = read_fasta(args[0])
     if len({len(s) for s in seqs}) != 1:
         sys.exit("sequences have different lengths: not an alignment")
@@ -204,7 +257,7 @@ def main():
             raise
         sys.exit(str(e))
     for k, ll in enumerate(loglk):
-        sys.stderr.write("TreeLogLk\t%s%d\t%.4f\n" % ("Round" if extra else "Length", k + 1, ll))
+        sys.stderr.write("TreeLogLk\t%s%d\t%.4f\n" % (label, k + 1, ll))
     print(tree)
 
 

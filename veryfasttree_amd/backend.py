@@ -52,7 +52,7 @@ HIT_F32 = np.dtype([("j", np.int32), ("dist", np.float32), ("weight", np.float32
 HIT_F64 = np.dtype([("j", np.int64), ("dist", np.float64), ("weight", np.float64), ("criterion", np.float64)])
 
 HOST_LIB_PATH = os.path.join(LIB_DIR, "libvft_host.so")
-HOST_EXPORTS = ["vft_nj_run", "vft_nj_newick", "vft_nj_ml_newick", "vft_nj_last_join_crcs", "vft_nj_last_stage_seconds", "vft_nj_last_walk_dual", "vft_nj_last_lane_exchange", "vft_nj_lane_share", "vft_nj_out_profile_block", "vft_nj_last_gamma", "vft_nj_make_matrix", "vft_tree_partitioning", "vft_knuth_stream", "vft_ml_lengths", "vft_gtr_tables",
+HOST_EXPORTS = ["vft_nj_run", "vft_nj_newick", "vft_nj_ml_newick", "vft_nj_last_join_crcs", "vft_nj_last_stage_seconds", "vft_nj_last_walk_dual", "vft_nj_last_lane_exchange", "vft_nj_lane_share", "vft_nj_out_profile_block", "vft_nj_last_gamma", "vft_nj_round_plan", "vft_nj_make_matrix", "vft_tree_partitioning", "vft_knuth_stream", "vft_ml_lengths", "vft_gtr_tables",
                 "vft_aa_model_tables", "vft_blosum45_tables", "vft_aa_model_as_distance_tables"]
 
 
@@ -60,7 +60,8 @@ class _NJOptions(C.Structure):
     _fields_ = [("fastest", I32), ("use_tophits_2nd", I32), ("tophits_mult", C.c_double), ("tophits_close", C.c_double),
                 ("tophits_refresh", C.c_double), ("topvisible_mult", C.c_double), ("stale_out_limit", C.c_double),
                 ("f_reset_out_profile", C.c_double), ("n_reset_out_profile", I32), ("tophits2_safety", I32),
-                ("tophits2_mult", C.c_double), ("tophits2_refresh", C.c_double), ("scoredist", I32), ("mllen", I32), ("me_nni", I32), ("ml_nni", I32), ("spr", I32), ("gtr", I32), ("aa_model", I32), ("comm", P), ("threads", I32), ("debug_flags", I32), ("gamma", I32), ("out_profile_parts", I32), ("slow", I32), ("intree", C.c_char_p), ("pseudo_weight", C.c_double)]
+                ("tophits2_mult", C.c_double), ("tophits2_refresh", C.c_double), ("scoredist", I32), ("mllen", I32), ("me_nni", I32), ("ml_nni", I32), ("spr", I32), ("gtr", I32), ("aa_model", I32), ("comm", P), ("threads", I32), ("debug_flags", I32), ("gamma", I32), ("out_profile_parts", I32), ("slow", I32), ("intree", C.c_char_p), ("pseudo_weight", C.c_double),
+                ("ml_accuracy", I32), ("slow_nni", I32), ("nni_rounds", I32), ("ml_nni_rounds", I32), ("spr_length", I32)]
 
 
 class _ExhaustiveBest(C.Structure):
@@ -255,10 +256,14 @@ def uniquify(codes):
 
 def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtype=np.float32, me_lengths=False,
               unique=None, scoredist=False, n_bootstrap=0, mllen=0, return_loglk=False, return_rates=False, me_nni=False, ml_nni=0, spr=0, gtr=False, return_gtr=False,
-              aa_model=None, comm=None, threads=1, debug_flags=0, gamma=False, out_profile_parts=0, slow=False, intree=None, pseudo=0.0):
+              aa_model=None, comm=None, threads=1, debug_flags=0, gamma=False, out_profile_parts=0, slow=False, intree=None, pseudo=0.0,
+              ml_accuracy=1, slow_nni=False, nni_rounds=None, ml_nni_rounds=None, spr_length=None):
     """The NJ phase of the whole alignment `codes_all` (duplicates included) as the reference's "NJ" tree string.
     intree (str): `-intree` - Newick text of a starting tree; the NJ phase does not run (vft_nj_options.intree).
     pseudo (float): `-pseudo W` - pseudocount distances in the minimum-evolution stages, 0 = off (vft_nj_options.pseudo_weight).
+    ml_accuracy (int): `-mlacc N`; slow_nni: `-slownni`; nni_rounds / ml_nni_rounds (int > 0): `-nni N` / `-mlnni N` (0 rounds are
+    me_nni=False with spr=0 / ml_nni=0); spr_length (int > 0): `-sprlength N`.  None = the reference's default (vft_nj_options.ml_accuracy
+    ... spr_length).
     make_ops(n_unique, n_pos) -> HipProfileOps for the unique sequences (max_nodes >= 3 * n_unique with me_lengths:
     then the tree carries the minimum-evolution branch lengths, the final output of -noml -nome -nosupport)."""
     lib = load_host_library()
@@ -273,10 +278,15 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
     ops = make_ops(n, L)
     if second_level is None:
         second_level = fastest
+    if nni_rounds is not None and int(nni_rounds) == 0:      # `-nni 0` also sets spr = 0 (VeryFastTree.cpp:72)
+        me_nni, spr = False, 0
+    if ml_nni_rounds is not None and int(ml_nni_rounds) == 0:
+        ml_nni = 0
     opt = _NJOptions(1 if fastest else 0, 1 if second_level else 0, 1.0, -1.0, 0.5 if fastest else 0.8, 1.5, 0.01, 0.02,
                      200, 3, 1.0, 0.6, 1 if scoredist else 0, int(mllen), 1 if me_nni else 0, int(ml_nni), int(spr), 1 if gtr else 0,
                      AA_MODELS[aa_model], comm.pointer() if comm is not None else None, int(threads), int(debug_flags), 1 if gamma else 0, int(out_profile_parts), 1 if slow else 0,
-                     None if intree is None else _intree_bytes(intree), float(pseudo))
+                     None if intree is None else _intree_bytes(intree), float(pseudo),
+                     1 if ml_accuracy is None else int(ml_accuracy), int(slow_nni), *(0 if v is None else int(v) for v in (nni_rounds, ml_nni_rounds, spr_length)))
     blob = b"".join(nm.encode() + b"\0" for nm in names)
     cap = 64 * len(names) + len(blob) + 1024
     out = C.create_string_buffer(cap)
@@ -301,6 +311,19 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
     if return_loglk:
         return out.value.decode(), loglk[:n_rounds.value]
     return out.value.decode()
+
+
+def round_plan(n_seqs, nni_rounds=None, ml_nni_rounds=None, spr=2):
+    """The rounds of the refinement stages (vft_nj_round_plan; no device): (minimum-evolution NNI rounds, ML NNI rounds, the 0-based ML
+    round behind which the NNI statistics are reset, [per SPR round the number of NNI rounds it runs behind])"""
+    lib = load_host_library()
+    out = np.zeros(3, np.int64)
+    behind = np.zeros(max(int(spr), 1), np.int64)
+    lib.vft_nj_round_plan.argtypes = [I64, I32, I32, I32, P, P, I64]
+    rc = lib.vft_nj_round_plan(int(n_seqs), int(nni_rounds or 0), int(ml_nni_rounds or 0), int(spr), _ptr(out), _ptr(behind), len(behind))
+    if rc != 0:
+        raise VftError("vft_nj_round_plan: bad arguments (a negative count?)")
+    return int(out[0]), int(out[1]), int(out[2]), [int(x) for x in behind[:int(spr)]]
 
 
 def pseudo_distances(dist, weight, pseudo, scoredist=False):

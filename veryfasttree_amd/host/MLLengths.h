@@ -613,7 +613,8 @@ namespace veryfasttree {
             bool useML = false;
             bool scoredist = false;      /* logCorrect flavour of the ME criterion (NJ.tcc:322-330) */
             double ftol = 0.001, atol = 1e-4, minDelta = 1.0e-4 /* MEMinDelta */;
-            int32_t mlAccuracy = 1;
+            int32_t mlAccuracy = 1;      /* `-mlacc N`: rounds per quartet (at least 2); from 2 on no alternative is dropped (NJ.tcc:4893, :4957) */
+            bool fastNNI = true;         /* false = `-slownni`: no subtree is skipped (NJ.tcc:6049) */
         };
 
         int64_t doNNI(const NNIParams &prm, std::vector<NNIStats> &stats, double &dMaxDelta) {
@@ -625,7 +626,7 @@ namespace veryfasttree {
             /* nodes whose subtree has been quiet for two rounds are not entered (NJ.tcc:6047-6075) */
             for (int64_t node = nSeqs; node < nNodes; node++) {
                 const NNIStats &st = stats[(size_t) node];
-                if (node != root && st.age >= 2 && st.subtreeAge >= 2 && st.support > supportThreshold) {
+                if (prm.fastNNI && node != root && st.age >= 2 && st.subtreeAge >= 2 && st.support > supportThreshold) {
                     int64_t q[4];
                     quartetNodes(node, q);
                     int i;
@@ -1315,7 +1316,7 @@ namespace veryfasttree {
             std::vector<char> traversal((size_t) nNodes, 0), upHave((size_t) nNodes, 0);
             for (int64_t node = nSeqs; node < nNodes; node++) {   /* quiet subtrees are not entered (NJ.tcc:6047-6075) */
                 const NNIStats &st = stats[(size_t) node];
-                if (node != root && st.age >= 2 && st.subtreeAge >= 2 && st.support > supportThreshold) {
+                if (prm.fastNNI && node != root && st.age >= 2 && st.subtreeAge >= 2 && st.support > supportThreshold) {
                     int64_t q[4];
                     quartetNodes(node, q);
                     int i;

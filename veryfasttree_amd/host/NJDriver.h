@@ -75,6 +75,13 @@ namespace veryfasttree {
            updateBranchLengths - pulls its distances towards their weighted mean with this weight; 0 = off.  No dual commands then (the
            workgroups would compare distances without pseudocounts). */
         double pseudoWeight = 0.0;
+        /* the thorough search (include/vft_host.h, vft_nj_options.ml_accuracy ... spr_length), each at the reference's default:
+           `-mlacc N` (rounds per quartet, no alternative dropped, rounds of setMLGtr, the supports' second pass), `-slownni` (no subtree
+           skipped), `-nni N` / `-mlnni N` (0: round(4 log2 n) / round(2 log2 n) rounds), `-sprlength N` (the longest SPR chain) */
+        int mlAccuracy = 1;
+        bool slowNNI = false;
+        int nniRounds = 0, mlNNIRounds = 0;
+        int sprLength = 10;
         /* > 1: the refinement stages follow the reference's `-threads T` schedule (MLLengths.h "the subtree schedule") */
         int threads = 1;
         bool gamma = false;          /* `-gamma`: rescale the final lengths to a fitted discrete Gamma (MLLengths::branchlengthScale) */
@@ -95,6 +102,20 @@ namespace veryfasttree {
            the lowest criterion over all pairs of active nodes, the first (i, j) among equals (the reference at one thread) */
         bool slow = false;
     };
+
+    /* The refinement rounds of a run (VeryFastTreeImpl.tcc:145-149, :187-198), pure arithmetic - exported as vft_nj_round_plan:
+       `-nni N` / `-mlnni N` (rounds > 0) replace round(4 log2 n) / round(2 log2 n); SPR round k runs behind NNI round i (0-based)
+       when (i + 1) is a multiple of nniToDo / (spr + 1) - never inside the loop when that quotient is 0, the rounds left over run
+       behind the last NNI round */
+    inline int64_t meNNIRoundsToDo(int64_t nSeqs, int64_t rounds) {
+        return rounds > 0 ? rounds : (int64_t) (0.5 + 4.0 * std::log((double) nSeqs) / std::log(2.0));
+    }
+    inline int64_t mlNNIRoundsToDo(int64_t nSeqs, int64_t rounds) {
+        return rounds > 0 ? rounds : (int64_t) (0.5 + 2.0 * std::log((double) nSeqs) / std::log(2.0));
+    }
+    inline bool sprBehindNNIRound(int64_t i, int64_t nniToDo, int64_t spr) {
+        return nniToDo / (spr + 1) > 0 && ((i + 1) % (nniToDo / (spr + 1))) == 0;
+    }
 
     template<typename REAL>
     class NJDriver {
@@ -819,9 +840,10 @@ namespace veryfasttree {
             typename MLLengths<REAL>::NNIParams prm;
             prm.useML = false;
             prm.scoredist = opt.scoredist;
+            prm.fastNNI = !opt.slowNNI;
             std::vector<typename MLLengths<REAL>::NNIStats> stats;
             tree.initNNIStats(stats);
-            const int64_t nniToDo = (int64_t) (0.5 + 4.0 * std::log((double) nSeqs) / std::log(2.0));
+            const int64_t nniToDo = meNNIRoundsToDo(nSeqs, opt.nniRounds);
             int64_t total = 0, sprRemaining = spr;
             meNNIRoundsDone = 0;
             meSPRs = 0;
@@ -836,11 +858,11 @@ namespace veryfasttree {
                     if (nChange == 0) bConverged = true;
                 }
                 /* SPR rounds sit between thirds of the NNI rounds (VeryFastTreeImpl.tcc:187-198) */
-                if (sprRemaining > 0 && nniToDo / (spr + 1) > 0 && ((i + 1) % (nniToDo / (spr + 1))) == 0) {
+                if (sprRemaining > 0 && sprBehindNNIRound(i, nniToDo, spr)) {
                     {
                         const std::chrono::steady_clock::time_point ts = std::chrono::steady_clock::now();
                         if (std::getenv("VFT_STAGE_TRACE")) fprintf(stderr, "[stage] SPR round begins after %lld NNI rounds\n", (long long) (i + 1));
-                        meSPRs += tree.doSPR(opt.scoredist);
+                        meSPRs += tree.doSPR(opt.scoredist, opt.sprLength);
                         meSPRSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
                         if (std::getenv("VFT_STAGE_TRACE")) fprintf(stderr, "[stage] SPR round done: %.1f s of SPR so far, %lld moves\n", meSPRSeconds, (long long) meSPRs);
                     }
@@ -852,7 +874,7 @@ namespace veryfasttree {
             }
             while (sprRemaining > 0) {
                 const std::chrono::steady_clock::time_point ts = std::chrono::steady_clock::now();
-                meSPRs += tree.doSPR(opt.scoredist);
+                meSPRs += tree.doSPR(opt.scoredist, opt.sprLength);
                 meSPRSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
                 sprRemaining--;
             }
@@ -941,13 +963,15 @@ namespace veryfasttree {
                    rounds of DoNNI(useML) with the reference's convergence rule (one more round after the likelihood or
                    the best NNI stops improving by 0.1, NNI statistics reset for the last one), the rate categories
                    fitted after the first round, and a final pass over all lengths */
-                const int64_t MLnniToDo = (int64_t) (0.5 + 2.0 * std::log((double) nSeqs) / std::log(2.0));
+                const int64_t MLnniToDo = mlNNIRoundsToDo(nSeqs, opt.mlNNIRounds);
                 if (opt.threads > 1) ml.optimizeRoundThreaded(ftol, atol, opt.threads);
                 else ml.optimizeRound(ftol, atol);
                 typename MLLengths<REAL>::NNIParams prm;
                 prm.useML = true;
                 prm.ftol = ftol;
                 prm.atol = atol;
+                prm.mlAccuracy = opt.mlAccuracy;
+                prm.fastNNI = !opt.slowNNI;
                 std::vector<typename MLLengths<REAL>::NNIStats> stats;
                 ml.initNNIStats(stats);
                 double lastloglk = -1e20;
@@ -994,7 +1018,7 @@ namespace veryfasttree {
                     col[t] = (int32_t) pos;
                 }
                 const std::chrono::steady_clock::time_point ts = std::chrono::steady_clock::now();
-                const typename MLLengths<REAL>::SplitTests st = ml.testSplits(ftol, atol, nBootstrap, col.data());
+                const typename MLLengths<REAL>::SplitTests st = ml.testSplits(ftol, atol, nBootstrap, col.data(), /*alwaysSecondPass*/opt.mlAccuracy > 1);   /* NJ.tcc:6934, :6940 */
                 mlSupportSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
                 support = st.support;
                 mlBadSplits = st.nBadSplits;
@@ -1018,7 +1042,7 @@ namespace veryfasttree {
         }
 
         void fitGtr(MLLengths<REAL> &ml, int64_t &nLeafGaps, double ftol, double atol) {
-            const typename MLLengths<REAL>::GtrFit g = ml.setMLGtr(leafCodeCounts, nPos, /*mlAccuracy*/1, ftol, atol, opt.threads);
+            const typename MLLengths<REAL>::GtrFit g = ml.setMLGtr(leafCodeCounts, nPos, opt.mlAccuracy, ftol, atol, opt.threads);
             for (int i = 0; i < 6; i++) gtrRates[i] = g.rates[i];
             for (int i = 0; i < 4; i++) gtrFreq[i] = g.freq[i];
             gtrFitted = true;

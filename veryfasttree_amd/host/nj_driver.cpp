@@ -195,6 +195,11 @@ static veryfasttree::NJOptions toOptions(const vft_nj_options *o) {
         opt.outProfileParts = o->out_profile_parts >= 2 ? o->out_profile_parts : 0;
         opt.slow = o->slow != 0;
         opt.pseudoWeight = o->pseudo_weight;
+        opt.mlAccuracy = o->ml_accuracy > 1 ? o->ml_accuracy : 1;
+        opt.slowNNI = o->slow_nni != 0;
+        opt.nniRounds = o->nni_rounds > 0 ? o->nni_rounds : 0;
+        opt.mlNNIRounds = o->ml_nni_rounds > 0 ? o->ml_nni_rounds : 0;
+        opt.sprLength = o->spr_length > 0 ? o->spr_length : 10;
         if (o->debug_flags & VFT_NJ_DEBUG_HOST_JOINS) opt.deviceJoins = false;
         if (o->debug_flags & VFT_NJ_DEBUG_HOST_LISTS) opt.deviceLists = false;
         if (o->debug_flags & VFT_NJ_DEBUG_HOST_RESET) opt.deviceReset = false;
@@ -292,6 +297,40 @@ static void checkPseudo(const vft_nj_options *o) {
                                     "six distances per quartet and no weights");
 }
 
+/* the thorough search (`-mlacc`, `-slownni`, `-nni`, `-mlnni`, `-sprlength`): refused before anything reaches the device, each message
+   names its member (include/vft_host.h, vft_nj_options.ml_accuracy ... spr_length) */
+static void checkThorough(const vft_nj_options *o) {
+    if (!o) return;
+    const struct {
+        const char *name, *flag;
+        int32_t value;
+    } members[5] = {{"ml_accuracy", "-mlacc", o->ml_accuracy}, {"slow_nni", "-slownni", o->slow_nni}, {"nni_rounds", "-nni", o->nni_rounds},
+                    {"ml_nni_rounds", "-mlnni", o->ml_nni_rounds}, {"spr_length", "-sprlength", o->spr_length}};
+    for (const auto &m: members)
+        if (m.value < 0)
+            throw std::invalid_argument(std::string("vft_nj_options.") + m.name + " (" + m.flag + ") is negative: 0 is the reference's default");
+    if (o->spr_length > 64)
+        throw std::invalid_argument("vft_nj_options.spr_length (-sprlength) is above 64: the chain buffers of MLLengths::sprAttempt hold 64 steps");
+}
+
+/* the rounds of the refinement stages (host/NJDriver.h meNNIRoundsToDo / mlNNIRoundsToDo / sprBehindNNIRound), pure host code */
+extern "C" int vft_nj_round_plan(int64_t nSeqs, int32_t nniRounds, int32_t mlNNIRounds, int32_t spr, int64_t *out, int64_t *sprBehind, int64_t cap) {
+    if (nSeqs < 1 || nniRounds < 0 || mlNNIRounds < 0 || spr < 0 || !out) return VFT_ERR_INVALID;
+    const int64_t nniToDo = veryfasttree::meNNIRoundsToDo(nSeqs, nniRounds), mlToDo = veryfasttree::mlNNIRoundsToDo(nSeqs, mlNNIRounds);
+    out[0] = nniToDo;
+    out[1] = mlToDo;
+    out[2] = mlToDo - 2;
+    int64_t k = 0;
+    for (int64_t i = 0; i < nniToDo && k < spr; i++)
+        if (veryfasttree::sprBehindNNIRound(i, nniToDo, spr)) {
+            if (sprBehind && k < cap) sprBehind[k] = i + 1;
+            k++;
+        }
+    for (; k < spr; k++)
+        if (sprBehind && k < cap) sprBehind[k] = nniToDo;
+    return VFT_OK;
+}
+
 extern "C" int vft_pseudo_distances(int32_t nProfiles, int32_t precision, const void *dist, const void *weight, double pseudoWeight, int32_t scoredist,
                                     double *out) {
     if ((nProfiles != 3 && nProfiles != 4) || (precision != 4 && precision != 8) || !dist || !weight || !out) return VFT_ERR_INVALID;
@@ -374,9 +413,13 @@ extern "C" int vft_nj_ml_newick(vft_ctx *ctx, const uint8_t *codes, int64_t nSeq
                                 int32_t ratesCap, int32_t *nRates, int32_t *ratecatOut, double *gtrOut, char *err, int32_t errLen) {
     if (!ctx || !codes || !uniqueFirst || !alnNext || !names || !outLen) return VFT_ERR_INVALID;
     try {
+        /* The option checks come first and look at `opt` alone: ctx is not dereferenced before runTree.  Callers rely on a refusal
+           reaching them with nothing uploaded, and the CPU tests (tests/test_thorough_cpu.py, tests/test_pseudo_cpu.py) hand over a
+           context that is no context: a check that needs ctx goes below these, never between or above them. */
         checkIntree(opt, nSeqs);
         checkSlow(opt);
         checkPseudo(opt);
+        checkThorough(opt);
         std::vector<double> ll, rates;
         std::vector<int64_t> ratecat;
         const std::string t = precision == 8 ? runTree<double>(ctx, codes, nSeqs, nPos, opt, meLengths != 0, nBootstrap, uniqueFirst, alnNext, nAll, names, ll, rates, ratecat, gtrOut)
@@ -440,6 +483,7 @@ extern "C" int vft_nj_run(vft_ctx *ctx, const uint8_t *codes, int64_t nSeqs, int
     try {
         if (opt && opt->intree) throw std::invalid_argument("vft_nj_run returns the joins of the NJ phase: with -intree there are none (use vft_nj_newick)");
         checkSlow(opt);
+        checkThorough(opt);
         *nJoins = precision == 8 ? runDriver<double>(ctx, codes, nSeqs, nPos, opt, maxJoins, joins, criterion)
                                  : runDriver<float>(ctx, codes, nSeqs, nPos, opt, maxJoins, joins, criterion);
         return VFT_OK;
