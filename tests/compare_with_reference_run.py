@@ -5,8 +5,8 @@
 
 One whole-pipeline run of this backend and one of the compiled reference (oracle/_ref/VeryFastTree, -threads 1 unless
 --threads) on the same synthetic alignment, compared: TreeLogLk lines, differing splits, branch lengths, supports, and
-the wall-clock of both.  flags: -gtr -lg -wag -double-precision -fastest (passed to the reference; mapped for the
-backend).  BASELINE config C2 = `10000 1000 -gtr`, C5 = `50000 300 --aa -lg -double-precision`."""
+the wall-clock of both.  flags: the reference's, e.g. -gtr -lg -wag -double-precision -fastest -spr 4 -mlacc 2 (passed to the reference;
+veryfasttree_amd.refflags maps them for the backend).  BASELINE config C2 = `10000 1000 -gtr`, C5 = `50000 300 --aa -lg -double-precision`."""
 import os
 import re
 import subprocess
@@ -20,6 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from veryfasttree_amd import HipProfileOps, synth  # noqa: E402
 from veryfasttree_amd.backend import nj_newick  # noqa: E402
+from veryfasttree_amd.refflags import from_reference_flags  # noqa: E402
 
 REFBIN = os.path.join(ROOT, "oracle", "_ref", "VeryFastTree")
 
@@ -63,23 +64,19 @@ def main():
             flags.append(a)
         i += 1
     mu, gap, seed, threads = float(opt["mu"]), float(opt["gap"]), int(opt["seed"]), int(opt["threads"])
-    dt = np.float64 if "-double-precision" in flags else np.float32
+    # --threads T: both sides run the T-thread schedule (the reference with -threads T, this backend with threads = T: the
+    # lanes of treePartitioning in lockstep); T = 1 is the one-thread order
+    run = from_reference_flags(([] if aa else ["-nt"]) + flags, threads=threads)
+    dt = run.dtype
     codes = synth.random_descent_codes(n, L, 20 if aa else 4, mu, gap, seed=seed)
     names = ["s%d" % k for k in range(n)]
     lines = []
     say = lambda s: (lines.append(s), print(s, flush=True))
     say("alignment %d x %d %s, mu %g gap %g seed %d; flags %s; %s" % (n, L, "aa" if aa else "nt", mu, gap, seed, " ".join(flags) or "(default)",
                                                                       "float64" if dt == np.float64 else "float32"))
-    # --threads T: both sides run the T-thread schedule (the reference with -threads T, this backend with threads = T: the
-    # lanes of treePartitioning in lockstep); T = 1 is the one-thread order
-    kw = dict(dtype=dt, me_lengths=True, me_nni=True, spr=2, ml_nni=20, n_bootstrap=1000, return_loglk=True, fastest="-fastest" in flags,
-              threads=threads, second_level="-fastest" in flags and threads == 1)
-    if aa:
-        kw["aa_model"] = "lg" if "-lg" in flags else "wag" if "-wag" in flags else "jtt"
-    elif "-gtr" in flags:
-        kw["gtr"] = True
     t0 = time.perf_counter()
-    tree, loglk = nj_newick(lambda m, Lp: HipProfileOps(m, Lp, 20 if aa else 4, dt, max_nodes=3 * m), codes, names, **kw)
+    tree, loglk = nj_newick(lambda m, Lp: HipProfileOps(m, Lp, run.n_codes, dt, max_nodes=3 * m), codes, names, me_lengths=True,
+                            n_bootstrap=run.n_bootstrap, return_loglk=True, **run.kwargs)
     t_gpu = time.perf_counter() - t0
     say("this backend, 1 x MI355X, schedule of %d thread(s): %.1f s; TreeLogLk %s" % (threads, t_gpu, " ".join("%.4f" % x for x in loglk)))
     if opt.get("noref"):

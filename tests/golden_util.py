@@ -16,6 +16,45 @@ def load(name):
     return dict(np.load(os.path.join(GOLDEN, name + ".npz")))
 
 
+def text(x):
+    return bytes(x).decode().strip()
+
+
+def reference_run(d, pre="", more=()):
+    """(RefRun, make_ops, names) of the reference run that a fixture records under `pre` ("" or "r<k>_"): its flags (and `more`, where
+    they leave out what the run had) through veryfasttree_amd.refflags, with the run's threads and start tree where the fixture has them"""
+    from veryfasttree_amd import HipProfileOps
+    from veryfasttree_amd.refflags import from_reference_flags
+    run = from_reference_flags(text(d[pre + "flags"]).split() + list(more), threads=int(d[pre + "threads"]) if pre + "threads" in d else None,
+                               intree_text=bytes(d[pre + "intree"]).decode() if pre + "intree" in d else None)
+    make = lambda n, L: HipProfileOps(n, L, run.n_codes, run.dtype, max_nodes=3 * n)
+    return run, make, ["s%d" % k for k in range(len(d["codes"]))]
+
+
+def assert_trees_match_the_reference(label, make, codes, names, kw, want, n_bootstrap=1000):
+    """nj_newick(**kw) against a whole run of the reference, want = its newick, newick_support and - of a run with an ML stage - loglk,
+    rates, ratecat: the TreeLogLk lines, the rates and the site categories, the tree without supports (topology first, then bytes), the
+    tree with supports"""
+    import re
+    from veryfasttree_amd.backend import nj_newick
+    if "loglk" not in want:
+        tree = nj_newick(make, codes, names, me_lengths=True, **kw)
+    else:
+        tree, loglk, rates, ratecat = nj_newick(make, codes, names, me_lengths=True, return_rates=True, **kw)
+        print(label, "TreeLogLk", list(loglk), "reference", list(want["loglk"]))
+        assert len(loglk) == len(want["loglk"])
+        assert np.allclose(loglk, want["loglk"], rtol=1e-4, atol=0)                    # the north star's bar
+        assert np.allclose(loglk, want["loglk"], rtol=2e-6 if kw["dtype"] == np.float32 else 1e-8, atol=6e-5), (loglk, want["loglk"])
+        assert np.array_equal(ratecat, want["ratecat"])
+        assert len(rates) == 20 and np.allclose(rates, want["rates"], rtol=0, atol=1e-6)   # printed with %f
+    ref = text(want["newick"])
+    strip = lambda t: re.sub(r":[0-9.eE+-]+", ":", t)
+    assert strip(tree) == strip(ref), "topology differs"
+    assert tree == ref
+    with_support = nj_newick(make, codes, names, me_lengths=True, n_bootstrap=n_bootstrap, **kw)
+    assert with_support == text(want["newick_support"])
+
+
 def dtype_of(d):
     return np.float32 if int(d["precisionBytes"]) == 4 else np.float64
 

@@ -6,8 +6,6 @@ import os
 import sys
 import zlib
 
-import numpy as np
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -17,7 +15,6 @@ def main():
     import torch
     import torch.distributed as dist
     import golden_util as G
-    from test_gpu_threads import AA
     name = sys.argv[1]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = 0 if os.environ.get("VFT_SAME_DEVICE") else int(os.environ.get("LOCAL_RANK", "0"))
@@ -29,23 +26,10 @@ def main():
         dist.init_process_group(os.environ.get("VFT_BACKEND", "nccl"))
         comm = TorchComm(dist, local)
     d = G.load(name)
-    flags = bytes(d["flags"]).decode().split()
-    codes_all = d["codes"]
-    nt = "-nt" in flags
-    dt = np.float64 if "-double-precision" in flags else np.float32
-    names = ["s%d" % k for k in range(len(codes_all))]
-    make = lambda n, L: HipProfileOps(n, L, 4 if nt else 20, dt, max_nodes=3 * n, device=local)
-    kw = dict(dtype=dt, me_lengths=True, threads=int(d["threads"]), comm=comm)
-    if not nt:
-        kw["aa_model"] = next((AA[f] for f in flags if f in AA), "jtt")
-    if "-noml" in flags:
-        kw.update(me_nni=True, spr=2)
-    elif "-mllen" in flags:
-        kw.update(mllen=20)
-    else:
-        kw.update(me_nni="-nome" not in flags, spr=0 if "-nome" in flags else 2, ml_nni=20, gtr="-gtr" in flags)
-    ml = "-noml" not in flags
-    tree = nj_newick(make, codes_all, names, return_loglk=ml, **kw)
+    run, _, names = G.reference_run(d)
+    make = lambda n, L: HipProfileOps(n, L, run.n_codes, run.dtype, max_nodes=3 * n, device=local)
+    ml = "ml_nni" in run.kwargs or "mllen" in run.kwargs
+    tree = nj_newick(make, d["codes"], names, me_lengths=True, comm=comm, return_loglk=ml, **run.kwargs)
     loglk = []
     if ml:
         tree, loglk = tree

@@ -21,12 +21,6 @@ def _make(dt):
     return lambda n, L: HipProfileOps(n, L, 20, dt, max_nodes=3 * n)
 
 
-def _model(d):
-    flags = bytes(d["flags"]).decode().split()
-    return "lg" if "-lg" in flags else "wag" if "-wag" in flags else "jtt", \
-        np.float64 if "-double-precision" in flags else np.float32, 1 if "-nocat" in flags else 20
-
-
 def test_min_evolution_nnis_and_sprs_on_proteins():
     """`VeryFastTree -noml` on a protein alignment: fastNJ, ME NNIs and SPRs under the BLOSUM45-derived distance matrix
     with the scoredist log-correction, ME lengths, local-bootstrap supports - byte for byte."""
@@ -47,10 +41,9 @@ def test_ml_lengths_on_proteins(name):
     (recomputeProfiles(tmatAsDist)), ML lengths on the NJ topology, CAT rates, SH-like supports."""
     from veryfasttree_amd.backend import nj_newick
     d = G.load(name)
-    model, dt, ncat = _model(d)
-    names = ["s%d" % k for k in range(len(d["codes"]))]
-    tree, loglk, rates, ratecat = nj_newick(_make(dt), d["codes"], names, dtype=dt, me_lengths=True, mllen=ncat, aa_model=model,
-                                            return_rates=True)
+    run, make, names = G.reference_run(d, more=["-nome", "-mllen"])   # (the recorded flags name the model, the precision and -nocat only)
+    dt = run.dtype
+    tree, loglk, rates, ratecat = nj_newick(make, d["codes"], names, me_lengths=True, return_rates=True, **run.kwargs)
     print(name, "loglk", loglk, "vs", d["loglk"])
     assert len(loglk) == len(d["loglk"])
     assert np.allclose(loglk, d["loglk"], rtol=1e-4, atol=0)          # north star: 1e-4 relative
@@ -62,7 +55,7 @@ def test_ml_lengths_on_proteins(name):
     dl = np.abs(lengths(tree) - lengths(ref))
     print(name, "printed lengths differing:", int((dl > 0).sum()), "of", len(dl), "max", dl.max())
     assert tree == ref            # ordered totals + glibc's exp / log: bit-identical likelihoods -> byte-identical tree
-    boot = nj_newick(_make(dt), d["codes"], names, dtype=dt, me_lengths=True, mllen=ncat, aa_model=model, n_bootstrap=1000)
+    boot = nj_newick(make, d["codes"], names, me_lengths=True, n_bootstrap=1000, **run.kwargs)
     refb = bytes(d["newick_support"]).decode().strip()
     assert no_support(boot) == no_support(refb)
     ds = np.abs(supports(boot) - supports(refb))
@@ -77,10 +70,9 @@ def test_full_protein_pipeline_matches_the_reference_run(name):
     round within 1e-4 relative (north star; observed: every printed digit) and the output byte for byte, supports included."""
     from veryfasttree_amd.backend import nj_newick
     d = G.load(name)
-    model, dt, ncat = _model(d)
-    names = ["s%d" % k for k in range(len(d["codes"]))]
-    kw = dict(dtype=dt, me_lengths=True, me_nni=True, spr=2, ml_nni=ncat, aa_model=model)
-    tree, loglk = nj_newick(_make(dt), d["codes"], names, return_loglk=True, **kw)
+    run, make, names = G.reference_run(d)
+    kw = dict(run.kwargs, me_lengths=True)
+    tree, loglk = nj_newick(make, d["codes"], names, return_loglk=True, **kw)
     want = d["loglk"]
     print(name, "rounds", len(loglk) - 1, "vs", len(want) - 1, "loglk", loglk, "vs", want)
     assert len(loglk) == len(want)
@@ -90,7 +82,7 @@ def test_full_protein_pipeline_matches_the_reference_run(name):
     dl = np.abs(lengths(tree) - lengths(ref))
     print(name, "printed lengths differing:", int((dl > 0).sum()), "of", len(dl), "max", dl.max())
     assert tree == ref
-    boot = nj_newick(_make(dt), d["codes"], names, n_bootstrap=1000, **kw)
+    boot = nj_newick(make, d["codes"], names, n_bootstrap=1000, **kw)
     refb = bytes(d["newick_support"]).decode().strip()
     assert no_support(boot) == no_support(refb)
     ds = np.abs(supports(boot) - supports(refb))

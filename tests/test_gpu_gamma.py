@@ -11,18 +11,11 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("name", ["gamma_nt_200", "gamma_nt_300_gtr", "gamma_aa_150_lg_double"])
 def test_gamma_rescaled_tree_matches_the_reference(name):
-    from veryfasttree_amd import HipProfileOps
     from veryfasttree_amd.backend import nj_newick, last_gamma
     d = G.load(name)
-    flags = bytes(d["flags"]).decode().split()
-    codes_all = d["codes"]
-    nt = "-nt" in flags
-    dt = np.float64 if "-double-precision" in flags else np.float32
-    names = ["s%d" % k for k in range(len(codes_all))]
-    kw = dict(dtype=dt, me_lengths=True, me_nni=True, spr=2, ml_nni=20, n_bootstrap=1000, gtr="-gtr" in flags, gamma=True, return_loglk=True)
-    if not nt:
-        kw["aa_model"] = "lg"
-    tree, loglk = nj_newick(lambda n, L: HipProfileOps(n, L, 4 if nt else 20, dt, max_nodes=3 * n), codes_all, names, **kw)
+    run, make, names = G.reference_run(d)
+    assert run.kwargs["gamma"]
+    tree, loglk = nj_newick(make, d["codes"], names, me_lengths=True, n_bootstrap=run.n_bootstrap, return_loglk=True, **run.kwargs)
     got, want = last_gamma(), d["gamma"]
     print(name, "Gamma(20) LogLk %.3f alpha %.3f rescale %.3f; reference" % got, list(want))
     assert np.allclose(loglk, d["loglk"], rtol=1e-4, atol=0)

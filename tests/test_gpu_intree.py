@@ -2,7 +2,6 @@
 tree (tools/gen_intree_fixtures.py, `VeryFastTree <flags> -threads T -seed 1 -intree T.nwk`) against this backend with the same text.  The
 node numbering of the parse decides device rows and the order of every later walk, so the trees must come out byte for byte."""
 import os
-import re
 import subprocess
 import sys
 
@@ -16,29 +15,17 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = ["intree_nt_4", "intree_nt_5", "intree_nt_200_me", "intree_nt_200_mllen", "intree_nt_200_full", "intree_nt_300_double_gtr",
             "intree_aa_120_lg", "intree_aa_100_wag_double_mllen", "intree_nt_62_dups_caterpillar", "intree_nt_400_t4"]
-AA = {"-lg": "lg", "-wag": "wag"}
 
 
 def case(name):
-    """the fixture, its start tree, and the arguments of nj_newick that spell its flags"""
-    from veryfasttree_amd import HipProfileOps
+    """the fixture, its start tree, and the arguments of nj_newick that spell its flags: kw without the stages (what reads the tree), and
+    the stages"""
     d = G.load(name)
-    flags = bytes(d["flags"]).decode().split()
-    nt = "-nt" in flags
-    dt = np.float64 if "-double-precision" in flags else np.float32
-    make = lambda n, L: HipProfileOps(n, L, 4 if nt else 20, dt, max_nodes=3 * n)
-    kw = dict(dtype=dt, threads=int(d["threads"]), intree=bytes(d["intree"]).decode())
-    if not nt:
-        kw["aa_model"] = next(AA[f] for f in flags if f in AA)
-    stages = {}
-    if "-noml" in flags:
-        assert "-nome" in flags
-    elif "-mllen" in flags:
-        assert "-nome" in flags
-        stages = dict(mllen=20)
-    else:
-        stages = dict(me_nni=True, spr=2, ml_nni=20, gtr="-gtr" in flags)
-    names = ["s%d" % k for k in range(len(d["codes"]))]
+    run, make, names = G.reference_run(d)
+    flags = G.text(d["flags"]).split()
+    assert "-nome" in flags or ("-noml" not in flags and "-mllen" not in flags)
+    stages = {key: v for key, v in run.kwargs.items() if key in ("me_nni", "spr", "mllen", "ml_nni", "gtr", "gamma")}
+    kw = {key: v for key, v in run.kwargs.items() if key not in stages}
     return d, flags, make, names, kw, stages
 
 
@@ -61,26 +48,9 @@ def test_the_tree_as_read_is_the_references_nj_line(name):
 def test_final_trees_match_the_reference(name):
     """the fixture's flags from the given tree: the tree without supports and the tree with them, byte for byte; for the ML cases the
     TreeLogLk lines, the rates and the site categories as the ml_* tests compare them"""
-    from veryfasttree_amd.backend import nj_newick
     d, flags, make, names, kw, stages = case(name)
-    dt = kw["dtype"]
-    if "-noml" in flags:
-        tree = nj_newick(make, d["codes"], names, me_lengths=True, **kw)
-    else:
-        tree, loglk, rates, ratecat = nj_newick(make, d["codes"], names, me_lengths=True, return_rates=True, **kw, **stages)
-        want = d["loglk"]
-        print(name, "TreeLogLk", list(loglk), "reference", list(want))
-        assert len(loglk) == len(want)
-        assert np.allclose(loglk, want, rtol=1e-4, atol=0)                    # the north star's bar
-        assert np.allclose(loglk, want, rtol=2e-6 if dt == np.float32 else 1e-8, atol=6e-5), (loglk, want)
-        assert np.array_equal(ratecat, d["ratecat"])
-        assert len(rates) == 20 and np.allclose(rates, d["rates"], rtol=0, atol=1e-6)   # printed with %f
-    ref = text(d, "newick")
-    strip = lambda t: re.sub(r":[0-9.eE+-]+", ":", t)
-    assert strip(tree) == strip(ref), "topology differs"
-    assert tree == ref
-    with_support = nj_newick(make, d["codes"], names, me_lengths=True, n_bootstrap=1000, **kw, **stages)
-    assert with_support == text(d, "newick_support")
+    want = {key: d[key] for key in ("newick", "newick_support", "loglk", "rates", "ratecat") if key in d}
+    G.assert_trees_match_the_reference(name, make, d["codes"], names, dict(kw, **stages), want)
 
 
 def test_mllen_with_gamma_on_a_given_tree():

@@ -22,30 +22,19 @@ LSUP = ["lsup_nt_16x1707", "lsup_nt_16x1707_boot100", "lsup_nt_12x3414_double", 
 
 def run_lsup(name, pairs=0, keep=None):
     """the fixture's alignment through nj_newick with the fixture's flags -> (tree, the reference's tree)"""
-    from veryfasttree_amd import HipProfileOps
     from veryfasttree_amd.backend import nj_newick
     d = G.load(name)
-    flags = bytes(d["flags"]).decode().split()
-    nt = "-nt" in flags
-    dt = np.float64 if "-double-precision" in flags else np.float32
-    n_boot = int(flags[flags.index("-boot") + 1]) if "-boot" in flags else 1000
-    codes = d["codes"]
-    names = ["s%d" % k for k in range(len(codes))]
+    run, make_ops, names = G.reference_run(d)
 
     def make(n, L):
-        ops = HipProfileOps(n, L, 4 if nt else 20, dt, max_nodes=3 * n)
+        ops = make_ops(n, L)
         if pairs:
             ops.debug_option(VFT_DEBUG_SUPPORT_PAIRS, pairs)
         if keep is not None:
             keep.append(ops)
         return ops
 
-    kw = dict(dtype=dt, me_lengths=True, n_bootstrap=n_boot)
-    if not nt:
-        kw["aa_model"] = "jtt"   # BLOSUM45 distances, scoredist log correction (no ML stage runs: the model itself is not used)
-    if "-nome" not in flags:
-        kw.update(me_nni=True, spr=2)
-    return nj_newick(make, codes, names, **kw), bytes(d["newick_support"]).decode().strip()
+    return nj_newick(make, d["codes"], names, me_lengths=True, n_bootstrap=run.n_bootstrap, **run.kwargs), G.text(d["newick_support"])
 
 
 @pytest.mark.parametrize("name", LSUP)

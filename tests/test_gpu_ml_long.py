@@ -7,45 +7,30 @@ numbers, at any length), and when the Jukes-Cantor totals are the reference's or
 import ctypes
 import re
 
-import numpy as np
 import pytest
 
 import golden_util as G
 
 pytestmark = pytest.mark.gpu
 VFT_DEBUG_ML_LONG = 16
-AA = {"-lg": "lg", "-wag": "wag"}
 
 
 def run_fixture(name, long_kernels, jc_exact, n_bootstrap=1000):
-    from veryfasttree_amd import HipProfileOps
     from veryfasttree_amd.backend import nj_newick
     d = G.load(name)
-    flags = bytes(d["flags"]).decode().split()
-    codes = d["codes"]
-    nt = "-nt" in flags
-    dt = np.float64 if "-double-precision" in flags else np.float32
-    names = ["s%d" % k for k in range(len(codes))]
+    # (the ml_* fixtures are `-nome -mllen` runs whose recorded flags name the model and the precision only)
+    run, make_ops, names = G.reference_run(d, more=["-nome", "-mllen"] if name.startswith("ml_") else [])
 
     def make(n, L):
-        ops = HipProfileOps(n, L, 4 if nt else 20, dt, max_nodes=3 * n)
+        ops = make_ops(n, L)
         if long_kernels:
             assert ops.lib.vft_debug_option(ops.ctx, ctypes.c_int32(VFT_DEBUG_ML_LONG), ctypes.c_int64(1)) == 0
         if jc_exact is not None:
             assert ops.lib.vft_set_jc_exact(ops.ctx, ctypes.c_int32(jc_exact)) == 0
         return ops
 
-    kw = dict(dtype=dt, me_lengths=True, n_bootstrap=n_bootstrap, threads=int(d["threads"]) if "threads" in d else 1)
-    if not nt:
-        kw["aa_model"] = next((AA[f] for f in flags if f in AA), "jtt")
-    if "-mllen" in flags or name.startswith("ml_"):   # (the protein `-nome -mllen` fixtures keep their kind in the name)
-        kw.update(mllen=1 if "-nocat" in flags else 20)
-    else:
-        spr = int(flags[flags.index("-spr") + 1]) if "-spr" in flags else 2
-        kw.update(me_nni="-nome" not in flags, spr=0 if "-nome" in flags else spr, ml_nni=1 if "-nocat" in flags else 20, gtr="-gtr" in flags)
-    tree = nj_newick(make, codes, names, **kw)
-    key = "newick_support" if n_bootstrap else "newick"
-    return tree, bytes(d[key]).decode().strip()
+    tree = nj_newick(make, d["codes"], names, me_lengths=True, n_bootstrap=n_bootstrap, **run.kwargs)
+    return tree, G.text(d["newick_support" if n_bootstrap else "newick"])
 
 
 # Jukes-Cantor (float, double, > 1 024 columns), GTR (float; double at 1 300 columns), LG / JTT proteins (the whole-column protein kernels'

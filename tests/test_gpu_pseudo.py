@@ -8,7 +8,6 @@ flagged and flagless steps interleaved in one session, both placements of the ma
 Whole runs of the reference with `-pseudo [W]` (tools/gen_pseudo_fixtures.py) against nj_newick(..., pseudo=W), byte for byte, and the
 same flags without the option against pseudo=0."""
 import ctypes as C
-import re
 
 import numpy as np
 import pytest
@@ -160,35 +159,19 @@ def test_step_w_without_a_server_is_a_state_error():
 
 
 # ------------------------------------------------------------------------------------------------ whole trees
-AA = {"-lg": "lg", "-wag": "wag"}
-
-
 def case(name, k, control):
     """run k of a fixture (or its control: the same flags without -pseudo) as the arguments of nj_newick"""
-    from veryfasttree_amd import HipProfileOps
     d = G.load(name)
     pre = "r%d_" % k
-    flags = bytes(d[pre + "flags"]).decode().split()
-    nt = "-nt" in flags
-    dt = np.float64 if "-double-precision" in flags else np.float32
-    make = lambda n, L: HipProfileOps(n, L, 4 if nt else 20, dt, max_nodes=3 * n)
-    kw = dict(dtype=dt, threads=int(d[pre + "threads"]), pseudo=0.0 if control else float(d[pre + "pseudo"]), slow="-slow" in flags)
-    if pre + "intree" in d:
-        kw["intree"] = bytes(d[pre + "intree"]).decode()
-    if not nt:
-        kw["aa_model"] = next((AA[f] for f in flags if f in AA), "jtt")
-    if "-noml" in flags:
-        stages = {} if "-nome" in flags else dict(me_nni=True, spr=2)
-    else:
-        stages = dict(me_nni=True, spr=2, ml_nni=20, gtr="-gtr" in flags)
-    names = ["s%d" % i for i in range(len(d["codes"]))]
+    run, make, names = G.reference_run(d, pre)
+    assert run.kwargs["pseudo"] == float(d[pre + "pseudo"])
+    kw = dict(run.kwargs, pseudo=0.0) if control else run.kwargs
     want = {key: d[pre + ("control_" if control else "") + key] for key in ("newick", "newick_support", "loglk", "rates", "ratecat")
             if pre + ("control_" if control else "") + key in d}
-    return d, flags, make, names, kw, stages, want
+    return d, G.text(d[pre + "flags"]).split(), make, names, kw, run.n_bootstrap, want
 
 
-def text(x):
-    return bytes(x).decode().strip()
+text = G.text
 
 
 @pytest.mark.parametrize("control", [False, True], ids=["pseudo", "control"])
@@ -196,50 +179,33 @@ def text(x):
 def test_trees_match_the_reference(name, k, control):
     """the run's flags, with and without supports, byte for byte; the ML runs add the TreeLogLk lines, the rates and the site categories
     as the ml_* / intree tests compare them.  control: the same flags without -pseudo through the same code with pseudo=0."""
-    from veryfasttree_amd.backend import nj_newick
-    d, flags, make, names, kw, stages, want = case(name, k, control)
-    dt = kw["dtype"]
-    if "-noml" in flags:
-        tree = nj_newick(make, d["codes"], names, me_lengths=True, **kw, **stages)
-    else:
-        tree, loglk, rates, ratecat = nj_newick(make, d["codes"], names, me_lengths=True, return_rates=True, **kw, **stages)
-        print(name, k, "TreeLogLk", list(loglk), "reference", list(want["loglk"]))
-        assert len(loglk) == len(want["loglk"])
-        assert np.allclose(loglk, want["loglk"], rtol=1e-4, atol=0)
-        assert np.allclose(loglk, want["loglk"], rtol=2e-6 if dt == np.float32 else 1e-8, atol=6e-5), (loglk, want["loglk"])
-        assert np.array_equal(ratecat, want["ratecat"])
-        assert len(rates) == 20 and np.allclose(rates, want["rates"], rtol=0, atol=1e-6)   # printed with %f
-    ref = text(want["newick"])
-    strip = lambda t: re.sub(r":[0-9.eE+-]+", ":", t)
-    assert strip(tree) == strip(ref), "topology differs"
-    assert tree == ref
-    n_boot = 0 if "-nosupport" in flags else 1000
-    with_support = nj_newick(make, d["codes"], names, me_lengths=True, n_bootstrap=n_boot, **kw, **stages)
-    assert with_support == text(want["newick_support"])
+    d, flags, make, names, kw, n_boot, want = case(name, k, control)
+    G.assert_trees_match_the_reference("%s %d" % (name, k), make, d["codes"], names, kw, want, n_bootstrap=n_boot)
 
 
 def test_one_tree_three_routes():
     """pseudo_nt_60_frag's `-noml -pseudo`: through the walk server, with a launch per step (the plain calls return the weights), and on
     the lockstep lanes of `-threads 4` (against that run's own fixture) - all three reach the reference"""
     from veryfasttree_amd.backend import nj_newick, DEBUG_NO_WALK_SERVER
-    d, flags, make, names, kw, stages, want = case("pseudo_nt_60_frag", 0, False)
+    d, flags, make, names, kw, _, want = case("pseudo_nt_60_frag", 0, False)
     assert flags == ["-nt", "-noml", "-pseudo"] and kw["threads"] == 1
     ref = text(want["newick_support"])
-    assert nj_newick(make, d["codes"], names, me_lengths=True, n_bootstrap=1000, **kw, **stages) == ref
-    assert nj_newick(make, d["codes"], names, me_lengths=True, n_bootstrap=1000, debug_flags=DEBUG_NO_WALK_SERVER, **kw, **stages) == ref
-    d4, flags4, make4, names4, kw4, stages4, want4 = case("pseudo_nt_60_frag", 6, False)
+    assert nj_newick(make, d["codes"], names, me_lengths=True, n_bootstrap=1000, **kw) == ref
+    assert nj_newick(make, d["codes"], names, me_lengths=True, n_bootstrap=1000, debug_flags=DEBUG_NO_WALK_SERVER, **kw) == ref
+    d4, flags4, make4, names4, kw4, _, want4 = case("pseudo_nt_60_frag", 6, False)
     assert flags4 == flags and kw4["threads"] == 4
-    assert nj_newick(make4, d4["codes"], names4, me_lengths=True, n_bootstrap=1000, **kw4, **stages4) == text(want4["newick_support"])
+    assert nj_newick(make4, d4["codes"], names4, me_lengths=True, n_bootstrap=1000, **kw4) == text(want4["newick_support"])
 
 
 def test_no_dual_commands_with_pseudocounts():
     """the comparison of a dual command works on distances without pseudocounts: none is sent while pseudo > 0 (the SPR chains wait for the
     host's verdict, as with VFT_NJ_DEBUG_NO_WALK_DUAL); the control on the same alignment sends them"""
     from veryfasttree_amd.backend import nj_newick, last_walk_dual
-    d, flags, make, names, kw, stages, want = case("pseudo_nt_200_frag", 0, False)
-    me = dict(me_nni=True, spr=2)   # (the minimum-evolution stages are where the chains run)
-    nj_newick(make, d["codes"], names, me_lengths=True, **kw, **me)
+    d, flags, make, names, kw, _, want = case("pseudo_nt_200_frag", 0, False)
+    kw = dict(kw, ml_nni=0)   # (the minimum-evolution stages are where the chains run)
+    assert kw["me_nni"] and kw["spr"] == 2
+    nj_newick(make, d["codes"], names, me_lengths=True, **kw)
     assert last_walk_dual() == (0, 0)
-    nj_newick(make, d["codes"], names, me_lengths=True, **dict(kw, pseudo=0.0), **me)
+    nj_newick(make, d["codes"], names, me_lengths=True, **dict(kw, pseudo=0.0))
     sent, taken = last_walk_dual()
     assert sent > 0 and taken > 0

@@ -8,7 +8,6 @@ the ml_accuracy >= 2 branches of k_ml_quartet (three or more rounds per quartet,
 split tests, and walks in which no subtree is skipped.  thor_nt_300_chains has SPR chains beyond the default's ten steps (`-sprlength 30`
 and 64 move its topology); thor_nt_150_mllen is `-nome -mllen` with `-mlacc` (the supports' second pass, three rounds of the -gtr fit)."""
 import os
-import re
 import subprocess
 import sys
 
@@ -23,63 +22,26 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = {"thor_nt_150": 8, "thor_nt_60_gtr": 2, "thor_aa_60_lg": 3, "thor_aa_40_wag_double": 2, "thor_nt_400_noisy": 5,
             "thor_aa_150_noisy": 1, "thor_nt_30_x2200": 1, "thor_aa_24_x600_lg": 1, "thor_nt_300_chains": 2, "thor_nt_150_mllen": 2}   # name: runs
 RUNS = [(name, k) for name, n in FIXTURES.items() for k in range(n)]
-AA = {"-lg": "lg", "-wag": "wag"}
-COUNTS = {"-mlacc": "ml_accuracy", "-nni": "nni_rounds", "-mlnni": "ml_nni_rounds", "-sprlength": "spr_length"}
 
 
 def case(name, k):
     """run k of a fixture as the arguments of nj_newick"""
-    from veryfasttree_amd import HipProfileOps
     d = G.load(name)
     pre = "r%d_" % k
-    flags = bytes(d[pre + "flags"]).decode().split()
-    nt = "-nt" in flags
-    dt = np.float64 if "-double-precision" in flags else np.float32
-    make = lambda n, L: HipProfileOps(n, L, 4 if nt else 20, dt, max_nodes=3 * n)
-    if "-mllen" in flags:   # `-nome -mllen`: ML lengths, CAT and supports on the NJ topology
-        kw = dict(dtype=dt, threads=int(d[pre + "threads"]), mllen=20, gtr="-gtr" in flags)
-    else:
-        kw = dict(dtype=dt, threads=int(d[pre + "threads"]), me_nni=True, spr=int(flags[flags.index("-spr") + 1]) if "-spr" in flags else 2,
-                  slow_nni="-slownni" in flags)
-    for flag, key in COUNTS.items():
-        if flag in flags:
-            kw[key] = int(flags[flags.index(flag) + 1])
-    if not nt:
-        kw["aa_model"] = next((AA[f] for f in flags if f in AA), "jtt")
-    if "-noml" not in flags and "-mllen" not in flags:
-        kw.update(ml_nni=20, gtr="-gtr" in flags, gamma="-gamma" in flags)
-    names = ["s%d" % i for i in range(len(d["codes"]))]
+    run, make, names = G.reference_run(d, pre)
     want = {key: d[pre + key] for key in ("newick", "newick_support", "loglk", "rates", "ratecat") if pre + key in d}
-    return d, flags, make, names, kw, want
+    return d, G.text(d[pre + "flags"]).split(), make, names, run.kwargs, want
 
 
-def text(x):
-    return bytes(x).decode().strip()
+text = G.text
 
 
 @pytest.mark.parametrize("name,k", RUNS)
 def test_trees_match_the_reference(name, k):
     """the run's flags, without and with supports, byte for byte; the ML runs add the TreeLogLk lines, the rates and the site categories as
     the ml_* / pseudo tests compare them"""
-    from veryfasttree_amd.backend import nj_newick
     d, flags, make, names, kw, want = case(name, k)
-    dt = kw["dtype"]
-    if "-noml" in flags:
-        tree = nj_newick(make, d["codes"], names, me_lengths=True, **kw)
-    else:
-        tree, loglk, rates, ratecat = nj_newick(make, d["codes"], names, me_lengths=True, return_rates=True, **kw)
-        print(name, k, "TreeLogLk", list(loglk), "reference", list(want["loglk"]))
-        assert len(loglk) == len(want["loglk"])
-        assert np.allclose(loglk, want["loglk"], rtol=1e-4, atol=0)
-        assert np.allclose(loglk, want["loglk"], rtol=2e-6 if dt == np.float32 else 1e-8, atol=6e-5), (loglk, want["loglk"])
-        assert np.array_equal(ratecat, want["ratecat"])
-        assert len(rates) == 20 and np.allclose(rates, want["rates"], rtol=0, atol=1e-6)   # printed with %f
-    ref = text(want["newick"])
-    strip = lambda t: re.sub(r":[0-9.eE+-]+", ":", t)
-    assert strip(tree) == strip(ref), "topology differs"
-    assert tree == ref
-    with_support = nj_newick(make, d["codes"], names, me_lengths=True, n_bootstrap=1000, **kw)
-    assert with_support == text(want["newick_support"])
+    G.assert_trees_match_the_reference("%s %d" % (name, k), make, d["codes"], names, kw, want)
 
 
 def test_the_tool_runs_the_accuracy_recipe(tmp_path):

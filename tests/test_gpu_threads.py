@@ -12,32 +12,13 @@ from conftest import free_port, heavy
 
 pytestmark = pytest.mark.gpu
 
-AA = {"-lg": "lg", "-wag": "wag"}
-
-
 def run_case(name, n_bootstrap=0):
-    from veryfasttree_amd import HipProfileOps
     from veryfasttree_amd.backend import nj_newick
     d = G.load(name)
-    flags = bytes(d["flags"]).decode().split()
-    codes_all = d["codes"]
-    nt = "-nt" in flags
-    dt = np.float64 if "-double-precision" in flags else np.float32
-    names = ["s%d" % k for k in range(len(codes_all))]
-    make = lambda n, L: HipProfileOps(n, L, 4 if nt else 20, dt, max_nodes=3 * n)
-    kw = dict(dtype=dt, me_lengths=True, threads=int(d["threads"]), n_bootstrap=n_bootstrap, return_loglk=True)
-    if not nt:
-        kw["aa_model"] = next((AA[f] for f in flags if f in AA), "jtt")
-    if "-noml" in flags:
-        kw.update(me_nni=True, spr=2)
-    elif "-mllen" in flags:
-        kw.update(mllen=20)
-    else:
-        kw.update(me_nni="-nome" not in flags, spr=0 if "-nome" in flags else 2, ml_nni=20, gtr="-gtr" in flags)
-    if "-noml" in flags:
-        kw.pop("return_loglk")
-        return d, nj_newick(make, codes_all, names, **kw), []
-    tree, loglk = nj_newick(make, codes_all, names, **kw)
+    run, make, names = G.reference_run(d)
+    if "ml_nni" not in run.kwargs and "mllen" not in run.kwargs:
+        return d, nj_newick(make, d["codes"], names, me_lengths=True, n_bootstrap=n_bootstrap, **run.kwargs), []
+    tree, loglk = nj_newick(make, d["codes"], names, me_lengths=True, n_bootstrap=n_bootstrap, return_loglk=True, **run.kwargs)
     return d, tree, loglk
 
 

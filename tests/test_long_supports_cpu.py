@@ -66,19 +66,20 @@ def tool():
 
 
 def test_boot_option_parsing(tool):
-    assert tool.parse_boot(["in.fa"]) == 1000
-    assert tool.parse_boot(["in.fa", "-boot", "100"]) == 100
-    assert tool.parse_boot(["in.fa", "-double", "-boot", "1"]) == 1
-    assert tool.parse_boot(["in.fa", "-boot", "1001", "-mllen"]) == 1001
+    n_boot = lambda args: tool.translate(args)[1].n_bootstrap
+    assert n_boot(["in.fa"]) == 1000
+    assert n_boot(["in.fa", "-boot", "100"]) == 100
+    assert n_boot(["in.fa", "-double", "-boot", "1"]) == 1
+    assert n_boot(["in.fa", "-boot", "1001", "-mllen"]) == 1001
     # -boot 0 is -nosupport; -nosupport and -nj-lengths win over a count
-    assert tool.parse_boot(["in.fa", "-boot", "0"]) == tool.parse_boot(["in.fa", "-nosupport"]) == 0
-    assert tool.parse_boot(["in.fa", "-boot", "100", "-nosupport"]) == 0
-    assert tool.parse_boot(["in.fa", "-boot", "100"], nj_len=True) == 0
+    assert n_boot(["in.fa", "-boot", "0"]) == n_boot(["in.fa", "-nosupport"]) == 0
+    assert n_boot(["in.fa", "-boot", "100", "-nosupport"]) == 0
+    assert n_boot(["in.fa", "-boot", "100", "-nj-lengths"]) == 0
 
 
 @pytest.mark.parametrize("args", [["in.fa", "-boot"], ["in.fa", "-boot", "ten"], ["in.fa", "-boot", "2.5"], ["in.fa", "-boot", "-3"],
                                   ["in.fa", "-boot", "-nosupport"]])
 def test_boot_option_rejects_what_is_no_count(tool, args):
     with pytest.raises(SystemExit) as e:
-        tool.parse_boot(args)
+        tool.translate(args)
     assert "-boot" in str(e.value)

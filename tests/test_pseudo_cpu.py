@@ -131,15 +131,18 @@ def load_tool():
 
 def test_the_tool_parses_the_option():
     t = load_tool()
-    assert t.parse_pseudo(["in.fa", "-full"]) == (0.0, ["in.fa", "-full"])
-    assert t.parse_pseudo(["in.fa", "-full", "-pseudo"]) == (1.0, ["in.fa", "-full"])                      # last
-    assert t.parse_pseudo(["in.fa", "-pseudo", "-nosupport"]) == (1.0, ["in.fa", "-nosupport"])           # before another flag
-    assert t.parse_pseudo(["in.fa", "-pseudo", "0.5", "-full"]) == (0.5, ["in.fa", "-full"])
-    assert t.parse_pseudo(["in.fa", "-pseudo", "3"]) == (3.0, ["in.fa"])
-    assert t.parse_pseudo(["in.fa", "-pseudo", "0"]) == (0.0, ["in.fa"])
+    run_of = lambda args: t.translate(args)[1]
+    assert "pseudo" not in run_of(["in.fa", "-full"]).kwargs
+    assert run_of(["in.fa", "-full", "-pseudo"]).kwargs["pseudo"] == 1.0                                  # last
+    run = run_of(["in.fa", "-pseudo", "-nosupport"])                                                     # before another flag
+    assert run.kwargs["pseudo"] == 1.0 and run.n_bootstrap == 0
+    run = run_of(["in.fa", "-pseudo", "0.5", "-full"])
+    assert run.kwargs["pseudo"] == 0.5 and run.kwargs["ml_nni"] == 20
+    assert run_of(["in.fa", "-pseudo", "3"]).kwargs["pseudo"] == 3.0
+    assert run_of(["in.fa", "-pseudo", "0"]).kwargs["pseudo"] == 0.0
     for bad in ("-1", "-0.5", "nan", "inf"):
         with pytest.raises(SystemExit) as e:
-            t.parse_pseudo(["in.fa", "-pseudo", bad])
+            t.translate(["in.fa", "-pseudo", bad])
         assert "-pseudo" in str(e.value)
 
 

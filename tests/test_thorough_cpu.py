@@ -26,44 +26,59 @@ def load_tool():
 
 
 # ------------------------------------------------------------------------------------------------ the tool
+def asked(t, args):
+    """what tools/nj_tree.py hands to nj_newick for `args`, the thorough-search keywords and the stages they touch only"""
+    kw = t.translate(args)[1].kwargs
+    return {key: kw[key] for key in ("ml_accuracy", "slow_nni", "nni_rounds", "ml_nni_rounds", "spr_length", "me_nni", "spr", "ml_nni") if key in kw}
+
+
+FULL = dict(me_nni=True, spr=2, ml_nni=20)   # the stages of -full
+
+
 def test_the_tool_parses_the_options():
     t = load_tool()
-    assert t.parse_thorough(["in.fa", "-full"]) == ({}, ["in.fa", "-full"])
-    assert t.parse_thorough(["in.fa", "-full", "-spr", "4", "-mlacc", "2", "-slownni"]) == \
-        (dict(ml_accuracy=2, slow_nni=True), ["in.fa", "-full", "-spr", "4"])          # (-spr is not -sprlength)
-    assert t.parse_thorough(["in.fa", "-nni", "3", "-full", "-mlnni", "2", "-sprlength", "30"]) == \
-        (dict(nni_rounds=3, ml_nni_rounds=2, spr_length=30), ["in.fa", "-full"])
-    assert t.parse_thorough(["in.fa", "-full", "-nni", "0", "-mlnni", "0"]) == (dict(nni_rounds=0, ml_nni_rounds=0), ["in.fa", "-full"])
-    assert t.parse_thorough(["in.fa", "-sprlength", "64"])[0] == dict(spr_length=64)
+    assert asked(t, ["in.fa", "-full"]) == FULL
+    assert asked(t, ["in.fa", "-full", "-spr", "4", "-mlacc", "2", "-slownni"]) == \
+        dict(FULL, spr=4, ml_accuracy=2, slow_nni=True)                                 # (-spr is not -sprlength)
+    assert asked(t, ["in.fa", "-nni", "3", "-full", "-mlnni", "2", "-sprlength", "30"]) == \
+        dict(FULL, nni_rounds=3, ml_nni_rounds=2, spr_length=30)
+    assert asked(t, ["in.fa", "-full", "-nni", "0", "-mlnni", "0"]) == {}
+    assert asked(t, ["in.fa", "-full", "-sprlength", "64"])["spr_length"] == 64
     for bad in (["-mlacc"], ["-mlacc", "0"], ["-mlacc", "-1"], ["-mlacc", "two"], ["-nni", "-1"], ["-mlnni", "1.5"], ["-sprlength", "0"],
                 ["-sprlength", "65"], ["-nni", "-full"]):
-        with pytest.raises(SystemExit) as e:
-            t.parse_thorough(["in.fa"] + bad)
-        assert bad[0] in str(e.value), bad
-    assert "64" in str(pytest.raises(SystemExit, t.parse_thorough, ["in.fa", "-sprlength", "65"]).value)
+        for mode in ([], ["-full"]):
+            with pytest.raises(SystemExit) as e:
+                t.translate(["in.fa"] + mode + bad)
+            assert bad[0] in str(e.value), bad
+    assert "64" in str(pytest.raises(SystemExit, t.translate, ["in.fa", "-full", "-sprlength", "65"]).value)
 
 
 def test_the_tool_maps_zero_rounds_onto_the_existing_switches():
     t = load_tool()
-    assert t.thorough_stages(dict(nni_rounds=0), True, False) == dict(me_nni=False, spr=0)      # `-nni 0` also sets spr = 0
-    assert t.thorough_stages(dict(ml_nni_rounds=0), True, False) == dict(ml_nni=0)              # `-mlnni 0` is -noml
-    assert t.thorough_stages(dict(nni_rounds=3, ml_nni_rounds=2, ml_accuracy=2, slow_nni=True, spr_length=5), True, False) == \
-        dict(nni_rounds=3, ml_nni_rounds=2, ml_accuracy=2, slow_nni=True, spr_length=5)
-    assert t.thorough_stages({}, False, False) == {}
+    assert asked(t, ["in.fa", "-full", "-nni", "0"]) == dict(ml_nni=20)                         # `-nni 0` also sets spr = 0
+    assert asked(t, ["in.fa", "-full", "-mlnni", "0"]) == dict(me_nni=True, spr=2)              # `-mlnni 0` is -noml
+    assert asked(t, ["in.fa", "-full", "-nni", "3", "-mlnni", "2", "-mlacc", "2", "-slownni", "-sprlength", "5"]) == \
+        dict(FULL, nni_rounds=3, ml_nni_rounds=2, ml_accuracy=2, slow_nni=True, spr_length=5)
+    assert asked(t, ["in.fa"]) == {}
+    # the rule itself, as nj_newick applies it to nni_rounds=0 / ml_nni_rounds=0
+    from veryfasttree_amd.refflags import zero_round_stages
+    assert zero_round_stages(True, 2, 20, 0, None) == (False, 0, 20) and zero_round_stages(True, 2, 20, None, 0) == (True, 2, 0)
+    assert zero_round_stages(True, 2, 20, 3, 2) == zero_round_stages(True, 2, 20, None, None) == (True, 2, 20)
 
 
 def test_the_tool_refuses_an_option_without_its_stage():
     t = load_tool()
     for key, flag in (("ml_accuracy", "-mlacc"), ("slow_nni", "-slownni"), ("nni_rounds", "-nni"), ("ml_nni_rounds", "-mlnni"),
                       ("spr_length", "-sprlength")):
+        option = [flag] if flag == "-slownni" else [flag, "1"]
         with pytest.raises(SystemExit) as e:
-            t.thorough_stages({key: 1}, False, False)
+            t.translate(["in.fa"] + option)
         assert flag in str(e.value) and "-full" in str(e.value)
         if key != "ml_accuracy":                       # -mllen runs no NNI and no SPR round
             with pytest.raises(SystemExit):
-                t.thorough_stages({key: 1}, False, True)
+                t.translate(["in.fa", "-mllen"] + option)
     # the supports and the -gtr fit of -mllen read the accuracy (NJ.tcc:6934, :6462)
-    assert t.thorough_stages(dict(ml_accuracy=2), False, True) == dict(ml_accuracy=2)
+    assert asked(t, ["in.fa", "-mllen", "-mlacc", "2"]) == dict(ml_accuracy=2)
 
 
 # ------------------------------------------------------------------------------------------------ the driver's refusals

@@ -16,35 +16,12 @@ expected outputs) is written to tests/golden/; the keys follow bb_*.npz / ml_*.n
 """
 import os
 import re
-import subprocess
-import sys
-import tempfile
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from veryfasttree_amd import synth  # noqa: E402
-from veryfasttree_amd.backend import uniquify  # noqa: E402
-
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFBIN = os.path.join(ROOT, "oracle", "_ref", "VeryFastTree")
-
-
-def rd(n, L, nc, mu, gap, seed):
-    return lambda: synth.random_descent_codes(n, L, nc, mu, gap, seed)
-
-
-def first_unique(codes, k):
-    seen, rows = set(), []
-    for row in codes:
-        if row.tobytes() not in seen:
-            seen.add(row.tobytes())
-            rows.append(row)
-        if len(rows) == k:
-            return np.stack(rows)
-    raise AssertionError("fewer than %d unique rows" % k)
+import reference_run as R
+from reference_run import GOLDEN, REFBIN, first_unique, rd, run, synth
+from veryfasttree_amd.backend import uniquify  # noqa: E402 (reference_run puts the repository on the path)
 
 
 def dups_codes():
@@ -86,8 +63,7 @@ def caterpillar_62(_codes):
 def reference_tree(flags):
     """the start tree is what the reference itself prints for the alignment with `flags` (a root of three, its own labels)"""
     def make(codes, tmp, name, nc):
-        fa = os.path.join(tmp, name + "_start.fa")
-        synth.codes_to_fasta(codes, fa, synth.ALPHABET_AA if nc == 20 else synth.ALPHABET_NT)
+        fa = R.write_fasta(tmp, name + "_start", codes, nc)
         return run([REFBIN] + flags + ["-threads", "1", "-seed", "1", fa]).stdout.decode()
     return make
 
@@ -106,11 +82,6 @@ CASES = [
     ("intree_nt_400_t4", ["-nt"], 4, 4, rd(400, 150, 4, 0.06, 0.02, 81), random_tree(400, 107, False)),                            # thr_full_nt_400_t4's
 ]
 GAMMA_TOO = {"intree_nt_200_mllen"}   # the same once more with -gamma
-
-
-def run(cmd):
-    env = dict(os.environ, OMP_WAIT_POLICY="passive")
-    return subprocess.run(cmd, check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
 
 
 def split_top(s):
@@ -175,8 +146,7 @@ def node_arrays(log_text, nj_line, aln_to_uniq, n_unique):
 
 def gen_case(tmp, name, flags, nc, threads, make, start):
     codes = make()
-    fa = os.path.join(tmp, name + ".fa")
-    synth.codes_to_fasta(codes, fa, synth.ALPHABET_AA if nc == 20 else synth.ALPHABET_NT)
+    fa = R.write_fasta(tmp, name, codes, nc)
     text = start if isinstance(start, str) else start(codes, tmp, name, nc) if start is not caterpillar_62 else start(codes)
     nwk = os.path.join(tmp, name + ".nwk")
     with open(nwk, "w") as fh:
@@ -187,37 +157,25 @@ def gen_case(tmp, name, flags, nc, threads, make, start):
     # (the Map lines are only written at one thread; the parse and the numbering do not depend on the thread count, and the NJ line
     #  of the case's own thread count is asserted to be the same)
     run([REFBIN] + model + ["-threads", "1"] + base[2:] + ["-verbose", "6", "-noml", "-nome", "-nosupport", "-log", log, fa])
-    vtext = open(log, errors="replace").read()
-    mnj = re.search(r"^NJ\t(\(.*;)\s*$", vtext, re.M)
-    assert mnj, "no NJ tree line for " + name
+    vtext = R.read_log(log)
+    nj = R.nj_line(vtext)
     if threads > 1:
         run([REFBIN] + model + base + ["-verbose", "3", "-noml", "-nome", "-nosupport", "-log", log, fa])
-        mt = re.search(r"^NJ\t(\(.*;)\s*$", open(log, errors="replace").read(), re.M)
-        assert mt and mt.group(1) == mnj.group(1), name + ": the NJ line depends on the thread count"
+        assert R.nj_line(R.read_log(log)) == nj, name + ": the NJ line depends on the thread count"
     unique_first, aln_next = uniquify(codes)
     aln_to_uniq = np.full(len(codes), -1, np.int64)
     for u, k in enumerate(unique_first):
         while k >= 0:
             aln_to_uniq[k] = u
             k = aln_next[k]
-    parent, child, root = node_arrays(vtext, mnj.group(1), aln_to_uniq, len(unique_first))
-    out = dict(codes=codes, intree=np.frombuffer(text.encode(), dtype=np.uint8), threads=np.int64(threads),
-               flags=np.frombuffer(" ".join(flags).encode(), dtype=np.uint8), nj_newick=np.frombuffer(mnj.group(1).encode(), dtype=np.uint8),
+    parent, child, root = node_arrays(vtext, nj, aln_to_uniq, len(unique_first))
+    out = dict(codes=codes, intree=R.as_bytes(text), threads=np.int64(threads), flags=R.as_bytes(" ".join(flags)), nj_newick=R.as_bytes(nj),
                parent=parent, child=child, root=np.int64(root))
     for tag, more in [("", [])] + ([("gamma_", ["-gamma"])] if name in GAMMA_TOO else []):
-        res = run([REFBIN] + flags + more + base + ["-nosupport", "-log", log, fa])
-        ltext = open(log, errors="replace").read()
-        res2 = run([REFBIN] + flags + more + base + [fa])
-        out[tag + "newick"] = np.frombuffer(res.stdout, dtype=np.uint8)
-        out[tag + "newick_support"] = np.frombuffer(res2.stdout, dtype=np.uint8)
-        if "-noml" not in flags:
-            ll = [float(m.group(1)) for m in re.finditer(r"^TreeLogLk\t\S+\t(\S+)", ltext, re.M)]
-            assert ll, "no TreeLogLk lines for " + name
-            out[tag + "loglk"] = np.array(ll)
-            out[tag + "rates"] = np.array([float(x) for x in re.search(r"^Rates((?: \S+)+)$", ltext, re.M).group(1).split()])
-            out[tag + "ratecat"] = np.array([int(x) - 1 for x in re.search(r"^SiteCategories((?: \d+)+)$", ltext, re.M).group(1).split()], dtype=np.int32)
+        for key, v in R.one_run(tmp, name + tag, fa, flags + more, threads, nwk).items():
+            out[tag + key] = v
         if more:
-            m = re.search(r"Gamma\(20\) LogLk = (\S+) alpha = (\S+) rescaling lengths by (\S+)", ltext)
+            m = re.search(r"Gamma\(20\) LogLk = (\S+) alpha = (\S+) rescaling lengths by (\S+)", R.read_log(os.path.join(tmp, name + tag + ".log")))
             assert m, name + ": no Gamma(20) line"
             out["gamma"] = np.array([float(m.group(k)) for k in (1, 2, 3)])
     dst = os.path.join(GOLDEN, name + ".npz")
@@ -225,19 +183,5 @@ def gen_case(tmp, name, flags, nc, threads, make, start):
     return "%-32s %4d rows %4d unique  %4d nodes  root %d  %7.1f KiB" % (name, len(codes), len(unique_first), len(parent), root, os.path.getsize(dst) / 1024.0)
 
 
-def main():
-    args = sys.argv[1:]
-    jobs = 4
-    if "--jobs" in args:
-        k = args.index("--jobs")
-        jobs = int(args[k + 1])
-        del args[k:k + 2]
-    assert os.path.exists(REFBIN), "build the reference first: make -C oracle ref"
-    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(jobs) as pool:
-        futs = [pool.submit(gen_case, tmp, *c) for c in CASES if not args or c[0] in args]
-        for f in futs:
-            print(f.result(), flush=True)
-
-
 if __name__ == "__main__":
-    main()
+    R.main(gen_case, CASES)

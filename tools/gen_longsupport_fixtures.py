@@ -13,36 +13,18 @@ Only data (inputs and expected outputs) is written to tests/golden/: codes, flag
 """
 import os
 import re
-import subprocess
-import sys
-import tempfile
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from veryfasttree_amd import synth  # noqa: E402
+import reference_run as R
+from reference_run import GOLDEN, REFBIN, first_unique, run, synth
 
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFBIN = os.path.join(ROOT, "oracle", "_ref", "VeryFastTree")
 NOCODE = 127
 MIN_DISTINCT_SUPPORTS = 3
 
 
 def rd(n, L, nc, mu, gap, seed):
     return lambda: first_unique(synth.random_descent_codes(2 * n, L, nc, mu, gap, seed), n)
-
-
-def first_unique(codes, k):
-    seen, rows = set(), []
-    for row in codes:
-        if row.tobytes() not in seen:
-            seen.add(row.tobytes())
-            rows.append(row)
-        if len(rows) == k:
-            return np.stack(rows)
-    raise AssertionError("fewer than %d unique rows" % k)
 
 
 def gappy_codes():
@@ -67,11 +49,6 @@ CASES = [
 ]
 
 
-def run(cmd):
-    env = dict(os.environ, OMP_WAIT_POLICY="passive")
-    return subprocess.run(cmd, check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
-
-
 def supports_of(tree):
     return re.findall(r"\)([0-9.]+):", tree)
 
@@ -79,40 +56,21 @@ def supports_of(tree):
 def gen_case(tmp, name, flags, nc, make):
     codes = make()
     assert len({r.tobytes() for r in codes}) == len(codes), name + ": duplicate rows"
-    fa = os.path.join(tmp, name + ".fa")
-    synth.codes_to_fasta(codes, fa, synth.ALPHABET_AA if nc == 20 else synth.ALPHABET_NT)
+    fa = R.write_fasta(tmp, name, codes, nc)
     log = os.path.join(tmp, name + ".log")
     res = run([REFBIN] + flags + ["-threads", "1", "-log", log, fa])
-    ltext = open(log, errors="replace").read()
-    mnj = re.search(r"^NJ\t(\(.*;)\s*$", ltext, re.M)
-    mme = re.search(r"^ME_Lengths\t(\(.*;)\s*$", ltext, re.M)
-    assert mnj and mme, name + ": no NJ / ME_Lengths line"
+    ltext = R.read_log(log)
     tree = res.stdout.decode()
     sup = supports_of(tree)
     assert len(sup) == len(codes) - 3, "%s: %d supports for %d sequences" % (name, len(sup), len(codes))
     distinct = sorted(set(sup))
     assert len(distinct) >= MIN_DISTINCT_SUPPORTS, "%s: supports %s - choose another mutation rate" % (name, distinct)
     dst = os.path.join(GOLDEN, name + ".npz")
-    np.savez_compressed(dst, codes=codes, flags=np.frombuffer(" ".join(flags).encode(), dtype=np.uint8),
-                        newick_support=np.frombuffer(res.stdout, dtype=np.uint8), nj_newick=np.frombuffer(mnj.group(1).encode(), dtype=np.uint8),
-                        me_lengths=np.frombuffer(mme.group(1).encode(), dtype=np.uint8), n_distinct_supports=np.int64(len(distinct)))
+    np.savez_compressed(dst, codes=codes, flags=R.as_bytes(" ".join(flags)), newick_support=R.as_bytes(res.stdout), nj_newick=R.as_bytes(R.nj_line(ltext)),
+                        me_lengths=R.as_bytes(R.nj_line(ltext, "ME_Lengths")), n_distinct_supports=np.int64(len(distinct)))
     assert os.path.getsize(dst) < (1 << 20), name + ": larger than a committed file may be"
     return "%-28s %3d x %5d  %2d distinct supports %s  %6.1f KiB" % (name, codes.shape[0], codes.shape[1], len(distinct), " ".join(distinct), os.path.getsize(dst) / 1024.0)
 
 
-def main():
-    args = sys.argv[1:]
-    jobs = 4
-    if "--jobs" in args:
-        k = args.index("--jobs")
-        jobs = int(args[k + 1])
-        del args[k:k + 2]
-    assert os.path.exists(REFBIN), "build the reference first: make -C oracle ref"
-    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(jobs) as pool:
-        futs = [pool.submit(gen_case, tmp, *c) for c in CASES if not args or c[0] in args]
-        for f in futs:
-            print(f.result(), flush=True)
-
-
 if __name__ == "__main__":
-    main()
+    R.main(gen_case, CASES)

@@ -11,18 +11,14 @@ Alignments are synth.random_descent_codes plus planted rows; each `_double` case
 printed entry (the numeric_t roundings of seqDist and logCorrect are visible in the text), or the pair would pin nothing.
 """
 import os
-import subprocess
 import sys
 import tempfile
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from veryfasttree_amd import synth  # noqa: E402
+import reference_run as R
+from reference_run import GOLDEN, REFBIN, run, synth
 
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFBIN = os.path.join(ROOT, "oracle", "_ref", "VeryFastTree")
 NOCODE = synth.NOCODE
 
 
@@ -61,15 +57,10 @@ CASES = [
 def gen_case(tmp, name, flags, nc, make):
     codes = np.ascontiguousarray(make(), np.uint8)
     names = ["s%d" % k for k in range(len(codes))]   # what synth.codes_to_fasta writes
-    fa = os.path.join(tmp, name + ".fa")
-    synth.codes_to_fasta(codes, fa, synth.ALPHABET_AA if nc == 20 else synth.ALPHABET_NT)
-    res = subprocess.run([REFBIN] + flags + ["-makematrix", "-threads", "1", fa], check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-    text = res.stdout
+    text = run([REFBIN] + flags + ["-makematrix", "-threads", "1", R.write_fasta(tmp, name, codes, nc)]).stdout
     assert text.count(b"\n") == len(codes), "%s: %d lines for %d sequences" % (name, text.count(b"\n"), len(codes))
     dst = os.path.join(GOLDEN, name + ".npz")
-    np.savez_compressed(dst, codes=codes, names=np.frombuffer("\n".join(names).encode(), dtype=np.uint8),
-                        flags=np.frombuffer(" ".join(flags + ["-makematrix"]).encode(), dtype=np.uint8),
-                        text=np.frombuffer(text, dtype=np.uint8))
+    np.savez_compressed(dst, codes=codes, names=R.as_bytes("\n".join(names)), flags=R.as_bytes(" ".join(flags + ["-makematrix"])), text=R.as_bytes(text))
     return text, "%-24s %4d x %3d  %7.1f KiB" % (name, codes.shape[0], codes.shape[1], os.path.getsize(dst) / 1024.0)
 
 

@@ -20,19 +20,11 @@ r<k>_control_newick_support, r<k>_intree (when the run starts from a tree), and 
 r<k>_control_loglk / _control_rates / _control_ratecat.  Only data (inputs and expected outputs) is written to tests/golden/."""
 import os
 import re
-import subprocess
-import sys
-import tempfile
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from veryfasttree_amd import synth  # noqa: E402
-
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFBIN = os.path.join(ROOT, "oracle", "_ref", "VeryFastTree")
+import reference_run as R
+from reference_run import GOLDEN, REFBIN, run, synth
 
 
 def fragments(n, L, nc, seed, keep):
@@ -90,11 +82,6 @@ FILES = [
 ]
 
 
-def run(cmd):
-    env = dict(os.environ, OMP_WAIT_POLICY="passive")
-    return subprocess.run(cmd, check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env)
-
-
 def without_pseudo(flags):
     """the flags of the control run, and the weight the -pseudo run asked for"""
     k = flags.index("-pseudo")
@@ -104,42 +91,13 @@ def without_pseudo(flags):
         return flags[:k] + flags[k + 1:], 1.0
 
 
-def nj_line(log):
-    m = re.search(r"^NJ\t(\(.*;)\s*$", open(log, errors="replace").read(), re.M)
-    assert m, "no NJ line in " + log
-    return m.group(1)
-
-
 def one_run(tmp, tag, fa, flags, threads, intree):
-    """the reference with `flags`: tree without supports (+ the ML log lines), tree with supports"""
-    out = {}
-    at = lambda t: [REFBIN] + [f for f in flags if f != INTREE] + ["-threads", str(t), "-seed", "1"] + (["-intree", intree] if INTREE in flags else [])
-    cmd = at(threads)
-    log = os.path.join(tmp, tag + ".log")
-    res = run(cmd + ["-nosupport", "-log", log, fa])
-    ltext = open(log, errors="replace").read()
-    res2 = run(cmd + [fa])
-    out["newick"] = np.frombuffer(res.stdout, dtype=np.uint8)
-    out["newick_support"] = np.frombuffer(res2.stdout, dtype=np.uint8)
-    if threads > 1:
-        assert run(cmd + [fa]).stdout == res2.stdout, tag + ": two runs at %d threads print different trees" % threads
-        if INTREE not in flags:
-            log1 = os.path.join(tmp, tag + "_t1.log")
-            run(at(1) + ["-nosupport", "-log", log1, fa])
-            assert nj_line(log) == nj_line(log1), tag + ": the NJ line depends on the thread count"
-    if "-noml" not in flags:
-        ll = [float(m.group(1)) for m in re.finditer(r"^TreeLogLk\t\S+\t(\S+)", ltext, re.M)]
-        assert ll, "no TreeLogLk lines for " + tag
-        out["loglk"] = np.array(ll)
-        out["rates"] = np.array([float(x) for x in re.search(r"^Rates((?: \S+)+)$", ltext, re.M).group(1).split()])
-        out["ratecat"] = np.array([int(x) - 1 for x in re.search(r"^SiteCategories((?: \d+)+)$", ltext, re.M).group(1).split()], dtype=np.int32)
-    return out
+    return R.one_run(tmp, tag, fa, [f for f in flags if f != INTREE], threads, intree if INTREE in flags else None)
 
 
 def gen_file(tmp, name, nc, make, runs):
     codes = make()
-    fa = os.path.join(tmp, name + ".fa")
-    synth.codes_to_fasta(codes, fa, synth.ALPHABET_AA if nc == 20 else synth.ALPHABET_NT)
+    fa = R.write_fasta(tmp, name, codes, nc)
     out = dict(codes=codes, n_runs=np.int64(len(runs)))
     intree = os.path.join(tmp, name + ".nwk")
     if any(INTREE in flags for flags, _ in runs):
@@ -155,11 +113,11 @@ def gen_file(tmp, name, nc, make, runs):
         assert bytes(got["newick"]) != bytes(ctl["newick"]), tag + ": -pseudo prints the control's tree"
         assert "-nosupport" in flags or bytes(got["newick_support"]) != bytes(ctl["newick_support"]), tag + ": -pseudo prints the control's tree"
         pre = "r%d_" % k
-        out[pre + "flags"] = np.frombuffer(" ".join(f for f in flags if f != INTREE).encode(), dtype=np.uint8)
+        out[pre + "flags"] = R.as_bytes(" ".join(f for f in flags if f != INTREE))
         out[pre + "threads"] = np.int64(threads)
         out[pre + "pseudo"] = np.float64(weight)
         if INTREE in flags:
-            out[pre + "intree"] = np.frombuffer(open(intree, "rb").read(), dtype=np.uint8)
+            out[pre + "intree"] = R.as_bytes(open(intree, "rb").read())
         for key, v in got.items():
             out[pre + key] = v
         for key, v in ctl.items():
@@ -171,19 +129,5 @@ def gen_file(tmp, name, nc, make, runs):
     return "%-22s %4d x %4d  %d runs  %6.1f KiB\n%s" % (name, codes.shape[0], codes.shape[1], len(runs), os.path.getsize(dst) / 1024.0, "\n".join(lines))
 
 
-def main():
-    args = sys.argv[1:]
-    jobs = 4
-    if "--jobs" in args:
-        k = args.index("--jobs")
-        jobs = int(args[k + 1])
-        del args[k:k + 2]
-    assert os.path.exists(REFBIN), "build the reference first: make -C oracle ref"
-    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(jobs) as pool:
-        futs = [pool.submit(gen_file, tmp, *f) for f in FILES if not args or f[0] in args]
-        for f in futs:
-            print(f.result(), flush=True)
-
-
 if __name__ == "__main__":
-    main()
+    R.main(gen_file, FILES)

@@ -12,32 +12,11 @@ and expected outputs) is written to tests/golden/.
 """
 import os
 import re
-import subprocess
-import sys
-import tempfile
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from veryfasttree_amd import synth  # noqa: E402
-
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFBIN = os.path.join(ROOT, "oracle", "_ref", "VeryFastTree")
-
-
-def first_unique(codes, k):
-    """the first k distinct rows, in first-occurrence order"""
-    seen, rows = set(), []
-    for row in codes:
-        key = row.tobytes()
-        if key not in seen:
-            seen.add(key)
-            rows.append(row)
-        if len(rows) == k:
-            return np.stack(rows)
-    raise AssertionError("fewer than %d unique rows" % k)
+import reference_run as R
+from reference_run import GOLDEN, REFBIN, first_unique, rd, run, synth
 
 
 def mirror_codes():
@@ -45,10 +24,6 @@ def mirror_codes():
     x = synth.random_descent_codes(40, 30, 4, 0.08, 0.0, 51)
     y = synth.random_descent_codes(40, 30, 4, 0.08, 0.0, 52)
     return np.concatenate([np.concatenate([x, y], axis=1), np.concatenate([y, x], axis=1)], axis=0)
-
-
-def rd(n, L, nc, mu, gap, seed):
-    return lambda: synth.random_descent_codes(n, L, nc, mu, gap, seed)
 
 
 CASES = [
@@ -67,74 +42,43 @@ CASES = [
     ("slow_nt_257", ["-nt"], 4, lambda: first_unique(synth.random_descent_codes(330, 40, 4, 0.10, 0.02, 62), 257)),
 ]
 MLLEN_CASES = [
-    ("slow_mllen_nt_200", ["-nt", "-nocat"], rd(200, 120, 4, 0.05, 0.02, 21)),   # ml_nt_200's flags plus -slow
+    ("slow_mllen_nt_200", ["-nt", "-nocat"], 4, rd(200, 120, 4, 0.05, 0.02, 21)),   # ml_nt_200's flags plus -slow
 ]
-
-
-def run(cmd):
-    return subprocess.run(cmd, check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
 
 
 def gen_case(tmp, name, flags, nc, make):
     codes = make()
-    fa = os.path.join(tmp, name + ".fa")
-    synth.codes_to_fasta(codes, fa, synth.ALPHABET_AA if nc == 20 else synth.ALPHABET_NT)
+    fa = R.write_fasta(tmp, name, codes, nc)
     log = os.path.join(tmp, name + ".log")
     res = run([REFBIN] + flags + ["-slow", "-threads", "1", "-seed", "1", "-verbose", "3", "-noml", "-nome", "-nosupport", "-log", log, fa])
-    text = open(log).read() + "\n" + res.stderr.decode(errors="replace")
+    text = R.read_log(log) + "\n" + res.stderr.decode(errors="replace")
     joins, seen = [], set()
     for m in re.finditer(r"^Join\t(\d+)\t(\d+)\t(\S+)\tlambda\t\S+\tselfw\t\S+\t\S+\tnew\t(\d+)", text, re.M):
         if int(m.group(4)) not in seen:   # log and stderr may both carry the lines
             seen.add(int(m.group(4)))
             joins.append((int(m.group(1)), int(m.group(2)), int(m.group(4)), float(m.group(3))))
     assert joins, "no Join lines for " + name
-    mnj = re.search(r"^NJ\t(\(.*;)\s*$", text, re.M)
-    assert mnj, "no NJ tree line for " + name
     res2 = run([REFBIN] + flags + ["-slow", "-threads", "1", "-seed", "1", "-noml", "-nome", fa])
     dst = os.path.join(GOLDEN, name + ".npz")
     np.savez_compressed(dst, codes=codes, joins=np.array([j[:3] for j in joins], dtype=np.int64),
                         join_criterion=np.array([j[3] for j in joins], dtype=np.float64),
-                        newick=np.frombuffer(res.stdout, dtype=np.uint8),
-                        nj_newick=np.frombuffer(mnj.group(1).encode(), dtype=np.uint8),
-                        newick_support=np.frombuffer(res2.stdout, dtype=np.uint8),
-                        flags=np.frombuffer(" ".join(flags + ["-slow"]).encode(), dtype=np.uint8))
+                        newick=R.as_bytes(res.stdout), nj_newick=R.as_bytes(R.nj_line(text)), newick_support=R.as_bytes(res2.stdout),
+                        flags=R.as_bytes(" ".join(flags + ["-slow"])))
     return "%-24s %5d joins  %7.1f KiB" % (name, len(joins), os.path.getsize(dst) / 1024.0)
 
 
-def gen_mllen_case(tmp, name, flags, make):
+def gen_mllen_case(tmp, name, flags, nc, make):
     codes = make()
-    fa = os.path.join(tmp, name + ".fa")
-    synth.codes_to_fasta(codes, fa, synth.ALPHABET_NT)
-    log = os.path.join(tmp, name + ".log")
-    res = run([REFBIN] + flags + ["-slow", "-threads", "1", "-seed", "1", "-nome", "-mllen", "-nosupport", "-log", log, fa])
-    text = open(log).read()
-    ll = [float(m.group(1)) for m in re.finditer(r"^TreeLogLk\tLength\d+\t(\S+)\tMaxChange", text, re.M)]
-    assert ll, "no TreeLogLk lines for " + name
-    rates = [float(x) for x in re.search(r"^Rates((?: \S+)+)$", text, re.M).group(1).split()]
-    cats = [int(x) - 1 for x in re.search(r"^SiteCategories((?: \d+)+)$", text, re.M).group(1).split()]
-    res2 = run([REFBIN] + flags + ["-slow", "-threads", "1", "-seed", "1", "-nome", "-mllen", fa])
+    got = R.one_run(tmp, name, R.write_fasta(tmp, name, codes, nc), flags + ["-slow", "-nome", "-mllen"], 1)
     dst = os.path.join(GOLDEN, name + ".npz")
-    np.savez_compressed(dst, codes=codes, loglk=np.array(ll), newick=np.frombuffer(res.stdout, dtype=np.uint8),
-                        newick_support=np.frombuffer(res2.stdout, dtype=np.uint8), rates=np.array(rates),
-                        ratecat=np.array(cats, dtype=np.int32),
-                        flags=np.frombuffer(" ".join(flags + ["-slow"]).encode(), dtype=np.uint8))
-    return "%-24s %2d rounds  final logLk %.4f  %7.1f KiB" % (name, len(ll), ll[-1], os.path.getsize(dst) / 1024.0)
+    np.savez_compressed(dst, codes=codes, loglk=got["loglk"], newick=got["newick"], newick_support=got["newick_support"], rates=got["rates"],
+                        ratecat=got["ratecat"], flags=R.as_bytes(" ".join(flags + ["-slow"])))
+    return "%-24s %2d rounds  final logLk %.4f  %7.1f KiB" % (name, len(got["loglk"]), got["loglk"][-1], os.path.getsize(dst) / 1024.0)
 
 
-def main():
-    args = sys.argv[1:]
-    jobs = 4
-    if "--jobs" in args:
-        k = args.index("--jobs")
-        jobs = int(args[k + 1])
-        del args[k:k + 2]
-    assert os.path.exists(REFBIN), "build the reference first: make -C oracle ref"
-    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(jobs) as pool:
-        futs = [pool.submit(gen_case, tmp, *c) for c in CASES if not args or c[0] in args]
-        futs += [pool.submit(gen_mllen_case, tmp, *c) for c in MLLEN_CASES if not args or c[0] in args]
-        for f in futs:
-            print(f.result(), flush=True)
+def gen_any(tmp, name, *case):
+    return (gen_mllen_case if name.startswith("slow_mllen_") else gen_case)(tmp, name, *case)
 
 
 if __name__ == "__main__":
-    main()
+    R.main(gen_any, CASES + MLLEN_CASES)

@@ -18,20 +18,11 @@ Keys: codes, n_runs, and per run r<k>_flags, r<k>_threads, r<k>_expect, r<k>_new
 r<k>_control_newick_support, and for ML runs r<k>_loglk / _rates / _ratecat and r<k>_control_loglk / _control_rates / _control_ratecat.
 Only data (inputs and expected outputs) is written to tests/golden/."""
 import os
-import re
-import subprocess
-import sys
-import tempfile
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from veryfasttree_amd import synth  # noqa: E402
-
-GOLDEN = os.path.join(ROOT, "tests", "golden")
-REFBIN = os.path.join(ROOT, "oracle", "_ref", "VeryFastTree")
+import reference_run as R
+from reference_run import GOLDEN, one_run, strip_lengths, synth
 
 WITH_NUMBER = ("-mlacc", "-nni", "-mlnni", "-sprlength")
 DIFFERS, TOPOLOGY, EQUAL, SUPPORTS = "differs", "topology", "equal", "supports"
@@ -86,11 +77,6 @@ FILES = [
 ]
 
 
-def run(cmd):
-    env = dict(os.environ, OMP_WAIT_POLICY="passive")
-    return subprocess.run(cmd, check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=120)   # (a run takes seconds; the reference can spin for ever)
-
-
 def control_of(flags):
     """the flags without the five options"""
     out, k = [], 0
@@ -105,46 +91,10 @@ def control_of(flags):
     return out
 
 
-def nj_line(log):
-    m = re.search(r"^NJ\t(\(.*;)\s*$", open(log, errors="replace").read(), re.M)
-    assert m, "no NJ line in " + log
-    return m.group(1)
-
-
-def one_run(tmp, tag, fa, flags, threads):
-    """the reference with `flags`: tree without supports (+ the ML log lines), tree with supports"""
-    out = {}
-    at = lambda t: [REFBIN] + flags + ["-threads", str(t), "-seed", "1"]
-    cmd = at(threads)
-    log = os.path.join(tmp, tag + ".log")
-    res = run(cmd + ["-nosupport", "-log", log, fa])
-    ltext = open(log, errors="replace").read()
-    res2 = run(cmd + [fa])
-    out["newick"] = np.frombuffer(res.stdout, dtype=np.uint8)
-    out["newick_support"] = np.frombuffer(res2.stdout, dtype=np.uint8)
-    if threads > 1:
-        assert run(cmd + [fa]).stdout == res2.stdout, tag + ": two runs at %d threads print different trees" % threads
-        log1 = os.path.join(tmp, tag + "_t1.log")
-        run(at(1) + ["-nosupport", "-log", log1, fa])
-        assert nj_line(log) == nj_line(log1), tag + ": the NJ line depends on the thread count"
-    if "-noml" not in flags:
-        ll = [float(m.group(1)) for m in re.finditer(r"^TreeLogLk\t\S+\t(\S+)", ltext, re.M)]
-        assert ll, "no TreeLogLk lines for " + tag
-        out["loglk"] = np.array(ll)
-        out["rates"] = np.array([float(x) for x in re.search(r"^Rates((?: \S+)+)$", ltext, re.M).group(1).split()])
-        out["ratecat"] = np.array([int(x) - 1 for x in re.search(r"^SiteCategories((?: \d+)+)$", ltext, re.M).group(1).split()], dtype=np.int32)
-    return out
-
-
-def strip_lengths(t):
-    return re.sub(rb"\)[0-9.]+:", b"):", re.sub(rb":[0-9.eE+-]+", b":", bytes(t)))
-
-
 def gen_file(tmp, name, nc, shape, runs):
     n, L, mu, gaps, seed = shape
     codes = synth.random_descent_codes(n, L, nc, mu, gaps, seed)
-    fa = os.path.join(tmp, name + ".fa")
-    synth.codes_to_fasta(codes, fa, synth.ALPHABET_AA if nc == 20 else synth.ALPHABET_NT)
+    fa = R.write_fasta(tmp, name, codes, nc)
     out = dict(codes=codes, n_runs=np.int64(len(runs)))
     lines = []
     for k, (flags, threads, expect) in enumerate(runs):
@@ -163,9 +113,9 @@ def gen_file(tmp, name, nc, shape, runs):
         if expect == TOPOLOGY:
             assert strip_lengths(got["newick"]) != strip_lengths(ctl["newick"]), tag + ": expected another topology than the control's"
         pre = "r%d_" % k
-        out[pre + "flags"] = np.frombuffer(" ".join(flags).encode(), dtype=np.uint8)
+        out[pre + "flags"] = R.as_bytes(" ".join(flags))
         out[pre + "threads"] = np.int64(threads)
-        out[pre + "expect"] = np.frombuffer(expect.encode(), dtype=np.uint8)
+        out[pre + "expect"] = R.as_bytes(expect)
         for key, v in got.items():
             out[pre + key] = v
         for key, v in ctl.items():
@@ -177,19 +127,5 @@ def gen_file(tmp, name, nc, shape, runs):
     return "%-22s %4d x %4d  %d runs  %6.1f KiB\n%s" % (name, codes.shape[0], codes.shape[1], len(runs), os.path.getsize(dst) / 1024.0, "\n".join(lines))
 
 
-def main():
-    args = sys.argv[1:]
-    jobs = 4
-    if "--jobs" in args:
-        k = args.index("--jobs")
-        jobs = int(args[k + 1])
-        del args[k:k + 2]
-    assert os.path.exists(REFBIN), "build the reference first: make -C oracle ref"
-    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(jobs) as pool:
-        futs = [pool.submit(gen_file, tmp, *f) for f in FILES if not args or f[0] in args]
-        for f in futs:
-            print(f.result(), flush=True)
-
-
 if __name__ == "__main__":
-    main()
+    R.main(gen_file, FILES)

@@ -39,6 +39,8 @@ subtree is skipped in any NNI round.  -nni N / -mlnni N: N minimum-evolution / M
 they end the program with a message.
 -boot N: N resamples instead of 1000 for the supports, local (default mode) and SH-like (-mllen, -full) alike, as the reference's
 -boot; -boot 0 is -nosupport.  Local supports take every alignment the NJ phase takes (10 240 columns).
+-full, -mllen, -double, -aa / -jtt and -nj-lengths are this tool's own words; every other flag is the reference's and means what
+veryfasttree_amd/refflags.py says it means (a flag it does not know ends the program, as does a flag without its number).
 Sequence normalisation and uniquify follow Alignment.cpp:453-526 (U -> T, '.' -> '-', duplicates by sequence string in
 first-occurrence order; N -> X for nucleotides)."""
 import os, sys
@@ -47,6 +49,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from veryfasttree_amd import HipProfileOps
 from veryfasttree_amd.backend import make_matrix, nj_newick, VftError
+from veryfasttree_amd.refflags import from_reference_flags
 from veryfasttree_amd.synth import ALPHABET_AA, ALPHABET_NT, NOCODE
 
 
@@ -78,82 +81,46 @@ def codes_of(seqs, aa):
     return seqs, np.stack([lut[np.frombuffer(s.encode("ascii", "replace"), np.uint8)] for s in seqs])
 
 
-def parse_boot(args, nj_len=False):
-    """the number of resamples of the supports: `-boot N` (N >= 0; 0 = -nosupport), -nosupport / -nj-lengths 0, else 1000"""
-    n_boot = 1000
-    if "-boot" in args:
-        k = args.index("-boot")
+NEEDS_FULL = ("-mlacc", "-slownni", "-nni", "-mlnni", "-sprlength")
+
+
+def translate(args):
+    """the tool's command line -> (alignment file, refflags.RefRun of the reference command line it stands for, whether -nj-lengths was
+    given): the default mode is the reference's `-noml -nome`, -mllen its `-nome -mllen`, -full its own default; -double is
+    -double-precision, -aa / -jtt are the reference without -nt.  Ends the program with a message on anything that cannot run."""
+    if not args or args[0].startswith("-"):
+        sys.exit(__doc__)
+    path, args = args[0], list(args[1:])
+    full, mllen = "-full" in args, "-mllen" in args
+    if "-slow" in args and full:
+        sys.exit("-slow with -full is not built: use -slow alone (the tree of -slow -noml -nome) or with -mllen")
+    intree = None
+    if "-intree" in args:
+        if "-slow" in args:
+            sys.exit("-intree with -slow is not built")
+        k = args.index("-intree")
         if k + 1 >= len(args):
-            sys.exit("-boot needs a number of resamples")
-        try:
-            n_boot = int(args[k + 1])
-        except ValueError:
-            sys.exit("-boot needs a whole number of resamples, not '%s'" % args[k + 1])
-        if n_boot < 0:
-            sys.exit("-boot needs a number of resamples >= 0")
-    return 0 if ("-nosupport" in args or nj_len) else n_boot
-
-
-def parse_pseudo(args):
-    """`-pseudo [W]`: the token behind -pseudo is the weight if it is a number (a negative or non-finite one is refused), else the weight
-    is 1.0 and the token is left alone; returns (weight or 0.0 without the option, args without the option)"""
-    if "-pseudo" not in args:
-        return 0.0, list(args)
-    args = list(args)
-    k = args.index("-pseudo")
-    weight, used = 1.0, 1
-    if k + 1 < len(args):
-        try:
-            weight, used = float(args[k + 1]), 2
-        except ValueError:
-            pass
-    if not (weight >= 0.0) or weight == float("inf"):
-        sys.exit("-pseudo takes a weight >= 0, not '%s'" % args[k + 1])
-    del args[k:k + used]
-    return weight, args
-
-
-THOROUGH_COUNTS = {"-mlacc": ("ml_accuracy", 1), "-nni": ("nni_rounds", 0), "-mlnni": ("ml_nni_rounds", 0), "-sprlength": ("spr_length", 1)}   # flag: (keyword, least N)
-
-
-def parse_thorough(args):
-    """`-mlacc N` (N >= 1), `-slownni`, `-nni N`, `-mlnni N` (N >= 0), `-sprlength N` (1 .. 64): returns (the keywords of nj_newick that
-    were asked for, args without these options).  A flag without its whole number, or with one out of range, ends the program."""
-    args, kw = list(args), {}
-    if "-slownni" in args:
-        args.remove("-slownni")
-        kw["slow_nni"] = True
-    for flag, (key, least) in THOROUGH_COUNTS.items():
-        if flag not in args:
-            continue
-        k = args.index(flag)
-        try:
-            kw[key] = int(args[k + 1])
-        except (IndexError, ValueError):
-            sys.exit("%s needs a whole number" % flag)
-        if kw[key] < least or (flag == "-sprlength" and kw[key] > 64):
-            sys.exit("%s needs a number %s, not %d" % (flag, "from 1 to 64 (the SPR chain buffers hold 64 steps)" if flag == "-sprlength" else ">= %d" % least, kw[key]))
+            sys.exit("-intree needs a file")
+        with open(args[k + 1]) as fh:
+            intree = fh.read()
         del args[k:k + 2]
-    return kw, args
-
-
-def thorough_stages(kw, full, mllen):
-    """where the thorough-search options are valid: all of them with -full; -mlacc also with -mllen, whose SH-like supports and -gtr fit
-    read it (NJ.tcc:6934, :6462).  Returns the keywords for nj_newick - `-nni 0` as me_nni=False with spr=0 (VeryFastTree.cpp:72),
-    `-mlnni 0` as ml_nni=0 - or ends the program: an option that cannot take effect is not ignored."""
-    names = {"slow_nni": "-slownni"}
-    names.update({key: flag for flag, (key, _) in THOROUGH_COUNTS.items()})
-    for key in kw:
-        if not (full or (key == "ml_accuracy" and mllen)):
-            sys.exit("%s needs -full%s: without it the stage the option belongs to does not run" % (names[key], " or -mllen" if key == "ml_accuracy" else ""))
-    out = dict(kw)
-    if out.get("nni_rounds") == 0:
-        del out["nni_rounds"]
-        out.update(me_nni=False, spr=0)
-    if out.get("ml_nni_rounds") == 0:
-        del out["ml_nni_rounds"]
-        out["ml_nni"] = 0
-    return out
+    protein = any(a in args for a in ("-aa", "-jtt", "-wag", "-lg"))
+    ref = [] if protein else ["-nt"]
+    ref += ["-nome", "-mllen"] if mllen else [] if full else ["-noml", "-nome"]
+    ref += ["-double-precision" if a == "-double" else a for a in args if a not in ("-full", "-mllen", "-aa", "-jtt", "-nj-lengths")]
+    try:
+        run = from_reference_flags(ref, intree_text=intree)
+    except ValueError as e:
+        sys.exit(str(e))
+    # an option that cannot take effect is not ignored: all five with -full; -mlacc also with -mllen, whose SH-like supports and -gtr fit
+    # read it (NJ.tcc:6934, :6462)
+    for flag in NEEDS_FULL:
+        if flag in args and not (full or (flag == "-mlacc" and mllen)):
+            sys.exit("%s needs -full%s: without it the stage the option belongs to does not run" % (flag, " or -mllen" if flag == "-mlacc" else ""))
+    if run.other:
+        sys.exit("not built in this tool: -%s" % ", -".join(run.other))
+    nj_len = "-nj-lengths" in args
+    return path, run._replace(n_bootstrap=0 if nj_len else run.n_bootstrap), nj_len
 
 
 MAKEMATRIX_FLAGS = ("-makematrix", "-rawdist", "-aa", "-double")
@@ -183,52 +150,11 @@ def main():
     args = sys.argv[1:]
     if "-makematrix" in args:
         return main_makematrix(args)
-    pseudo, args = parse_pseudo(args)
-    thorough, args = parse_thorough(args)
-    if not args or args[0].startswith("-"):
-        sys.exit(__doc__)
-    fastest, double, nj_len = "-fastest" in args, "-double" in args, "-nj-lengths" in args
-    slow = "-slow" in args
-    if slow and fastest:
-        sys.exit("-slow and -fastest exclude each other")
-    if slow and "-full" in args:
-        sys.exit("-slow with -full is not built: use -slow alone (the tree of -slow -noml -nome) or with -mllen")
-    intree = None
-    if "-intree" in args:
-        if slow:
-            sys.exit("-intree with -slow is not built")
-        k = args.index("-intree")
-        if k + 1 >= len(args):
-            sys.exit("-intree needs a file")
-        with open(args[k + 1]) as fh:
-            intree = fh.read()
-        del args[k:k + 2]
-    mllen = 0
-    if "-mllen" in args:
-        mllen = 1 if "-nocat" in args else (int(args[args.index("-cat") + 1]) if "-cat" in args else 20)
-    n_boot = parse_boot(args, nj_len)
-    extra = dict(me_nni=True, spr=2, ml_nni=20) if "-full" in args else {}
-    if "-gtr" in args:
-        extra["gtr"] = True   # ME NNIs + SPRs, ML NNIs, CAT, SH supports
-    if "-spr" in args and extra:
-        extra["spr"] = int(args[args.index("-spr") + 1])
-    if "-threads" in args:   # the refinement stages on the schedule of a T-thread run of the reference (include/vft_host.h, vft_nj_options.threads)
-        extra["threads"] = int(args[args.index("-threads") + 1])
-    if "-gamma" in args and extra:
-        extra["gamma"] = True
-    label = "Round" if extra else "Length"   # of the TreeLogLk lines: by the stages that run, whatever -mlacc adds to a -mllen run
-    extra.update(thorough_stages(thorough, "-full" in args, mllen != 0))   # (behind -spr: `-nni 0` switches the SPR rounds off)
-    names, seqs = read_fasta(args[0])
+    path, run, nj_len = translate(args)
+    names, seqs = read_fasta(path)
     if len({len(s) for s in seqs}) != 1:
         sys.exit("sequences have different lengths: not an alignment")
-    aa = None
-    for flag, model in (("-aa", "jtt"), ("-jtt", "jtt"), ("-wag", "wag"), ("-lg", "lg")):
-        if flag in args:
-            aa = model
-    # Alignment.cpp:453-471: '.' -> '-' always; for nucleotides U -> T and N -> X (before the sequences are uniquified)
-    seqs = [s.upper().replace(".", "-") for s in seqs]
-    if aa is None:
-        seqs = [s.replace("U", "T").replace("N", "X") for s in seqs]
+    seqs, codes_all = codes_of(seqs, run.n_codes == 20)   # (the sequences are uniquified as strings, after the normalisation)
     first_of, last, unique_first = {}, {}, []
     aln_next = np.full(len(seqs), -1, np.int64)
     for k, s in enumerate(seqs):
@@ -238,24 +164,16 @@ def main():
         else:
             aln_next[last[s]] = k
         last[s] = k
-    lut = np.full(256, NOCODE, np.uint8)
-    for i, ch in enumerate(ALPHABET_AA if aa else ALPHABET_NT):
-        lut[ord(ch)] = i
-    codes_all = np.stack([lut[np.frombuffer(s.encode("ascii", "replace"), np.uint8)] for s in seqs])
-    n_unique = len(unique_first)
-    if n_unique < 3:
+    if len(unique_first) < 3:
         sys.exit("fewer than 3 unique sequences")
-    dt = np.float64 if double else np.float32
-    if aa:
-        extra["aa_model"] = aa
     try:
-        tree, loglk = nj_newick(lambda n, L: HipProfileOps(n, L, 20 if aa else 4, dt, max_nodes=3 * n), codes_all, names, fastest=fastest,
-                                dtype=dt, me_lengths=not nj_len, unique=(np.array(unique_first, np.int64), aln_next),
-                                n_bootstrap=n_boot, mllen=mllen, return_loglk=True, slow=slow, intree=intree, pseudo=pseudo, **extra)
+        tree, loglk = nj_newick(lambda n, L: HipProfileOps(n, L, run.n_codes, run.dtype, max_nodes=3 * n), codes_all, names, me_lengths=not nj_len,
+                                unique=(np.array(unique_first, np.int64), aln_next), n_bootstrap=run.n_bootstrap, return_loglk=True, **run.kwargs)
     except VftError as e:
-        if intree is None:
+        if "intree" not in run.kwargs:
             raise
         sys.exit(str(e))
+    label = "Round" if "ml_nni" in run.kwargs else "Length"   # of the TreeLogLk lines: by the stages that run, whatever -mlacc adds to a -mllen run
     for k, ll in enumerate(loglk):
         sys.stderr.write("TreeLogLk\t%s%d\t%.4f\n" % (label, k + 1, ll))
     print(tree)

@@ -10,6 +10,8 @@ import sys
 
 import numpy as np
 
+from .refflags import zero_round_stages
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 # VFT_LIB_DIR: a variant build of tools/ (veryfasttree_amd/build.py with VFT_EXTRA_HIPCC_FLAGS: both libraries in
 # build/variants/<hash>/); VFT_HIP_LIB: another build of the HIP library alone.  Never set by tests or bench.py.
@@ -84,6 +86,33 @@ def load_host_library():
 
 
 AA_MODELS = {None: 0, "": 0, "jtt": 1, "wag": 2, "lg": 3}
+# vft_nj_options as the reference's Options start out (include/vft_host.h); every member not named here starts at zero
+NJ_DEFAULTS = dict(tophits_mult=1.0, tophits_close=-1.0, topvisible_mult=1.5, stale_out_limit=0.01, f_reset_out_profile=0.02, n_reset_out_profile=200,
+                   tophits2_safety=3, tophits2_mult=1.0, tophits2_refresh=0.6, threads=1, ml_accuracy=1)
+NJ_SWITCHES = ("fastest", "use_tophits_2nd", "scoredist", "me_nni", "gtr", "gamma", "slow")
+
+
+def _nj_options(**members):
+    """vft_nj_options by member name: NJ_DEFAULTS, then `members` (None = the default).  use_tophits_2nd defaults to fastest and
+    tophits_refresh to 0.5 with fastest, else 0.8 (main.cpp:339-343); aa_model is a name of AA_MODELS, comm a TorchComm, intree text."""
+    m = dict(NJ_DEFAULTS, **{k: v for k, v in members.items() if v is not None})
+    fastest = bool(m.get("fastest"))
+    m.setdefault("use_tophits_2nd", fastest)
+    m.setdefault("tophits_refresh", 0.5 if fastest else 0.8)
+    m["aa_model"] = AA_MODELS[m.get("aa_model")]
+    if "comm" in m:
+        m["comm"] = m["comm"].pointer()
+    if "intree" in m:
+        m["intree"] = _intree_bytes(m["intree"])
+    opt = _NJOptions()
+    for name, ctype in _NJOptions._fields_:
+        if name in m:
+            v = m.pop(name)
+            setattr(opt, name, (1 if v else 0) if name in NJ_SWITCHES else int(v) if ctype is I32 else float(v) if ctype is C.c_double else v)
+    if m:
+        raise TypeError("vft_nj_options has no member %s" % ", ".join(sorted(m)))
+    return opt
+
 
 _ALLGATHER = C.CFUNCTYPE(C.c_int, P, I64, I32)
 
@@ -157,13 +186,9 @@ def nj_run(ops, codes, fastest=False, max_joins=-1, tophits_refresh=None, second
     lib = load_host_library()
     codes = np.ascontiguousarray(codes, np.uint8)
     n, L = codes.shape
-    if second_level is None:
-        second_level = fastest
-    opt = _NJOptions(1 if fastest else 0, 1 if second_level else 0, float(tophits_mult), -1.0,
-                     tophits_refresh if tophits_refresh is not None else (0.5 if fastest else 0.8), 1.5, 0.01, 0.02,
-                     200, 3, 1.0, 0.6, 1 if scoredist else 0, 0, 0, 0, 0, 0, AA_MODELS[aa_model],
-                     comm.pointer() if comm is not None else None, 1, int(debug_flags), 0, int(out_profile_parts), 1 if slow else 0,
-                     None if intree is None else _intree_bytes(intree))
+    # (ml_accuracy 0: the members behind intree as a zero-initialised caller leaves them - no stage that reads them runs here)
+    opt = _nj_options(fastest=fastest, use_tophits_2nd=second_level, tophits_mult=tophits_mult, tophits_refresh=tophits_refresh, scoredist=scoredist,
+                      aa_model=aa_model, comm=comm, debug_flags=debug_flags, out_profile_parts=out_profile_parts, slow=slow, intree=intree, ml_accuracy=0)
     joins = np.zeros((max(n - 3, 1), 3), np.int64)
     crit = np.zeros(max(n - 3, 1), np.float64)
     nj = I64(0)
@@ -262,7 +287,7 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
     intree (str): `-intree` - Newick text of a starting tree; the NJ phase does not run (vft_nj_options.intree).
     pseudo (float): `-pseudo W` - pseudocount distances in the minimum-evolution stages, 0 = off (vft_nj_options.pseudo_weight).
     ml_accuracy (int): `-mlacc N`; slow_nni: `-slownni`; nni_rounds / ml_nni_rounds (int > 0): `-nni N` / `-mlnni N` (0 rounds are
-    me_nni=False with spr=0 / ml_nni=0); spr_length (int > 0): `-sprlength N`.  None = the reference's default (vft_nj_options.ml_accuracy
+    me_nni=False with spr=0 / ml_nni=0: refflags.zero_round_stages); spr_length (int > 0): `-sprlength N`.  None = the reference's default (vft_nj_options.ml_accuracy
     ... spr_length).
     make_ops(n_unique, n_pos) -> HipProfileOps for the unique sequences (max_nodes >= 3 * n_unique with me_lengths:
     then the tree carries the minimum-evolution branch lengths, the final output of -noml -nome -nosupport)."""
@@ -276,17 +301,11 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
     codes = np.ascontiguousarray(codes_all[unique_first])
     n, L = codes.shape
     ops = make_ops(n, L)
-    if second_level is None:
-        second_level = fastest
-    if nni_rounds is not None and int(nni_rounds) == 0:      # `-nni 0` also sets spr = 0 (VeryFastTree.cpp:72)
-        me_nni, spr = False, 0
-    if ml_nni_rounds is not None and int(ml_nni_rounds) == 0:
-        ml_nni = 0
-    opt = _NJOptions(1 if fastest else 0, 1 if second_level else 0, 1.0, -1.0, 0.5 if fastest else 0.8, 1.5, 0.01, 0.02,
-                     200, 3, 1.0, 0.6, 1 if scoredist else 0, int(mllen), 1 if me_nni else 0, int(ml_nni), int(spr), 1 if gtr else 0,
-                     AA_MODELS[aa_model], comm.pointer() if comm is not None else None, int(threads), int(debug_flags), 1 if gamma else 0, int(out_profile_parts), 1 if slow else 0,
-                     None if intree is None else _intree_bytes(intree), float(pseudo),
-                     1 if ml_accuracy is None else int(ml_accuracy), int(slow_nni), *(0 if v is None else int(v) for v in (nni_rounds, ml_nni_rounds, spr_length)))
+    me_nni, spr, ml_nni = zero_round_stages(me_nni, spr, ml_nni, nni_rounds, ml_nni_rounds)
+    opt = _nj_options(fastest=fastest, use_tophits_2nd=second_level, scoredist=scoredist, mllen=mllen, me_nni=me_nni, ml_nni=ml_nni, spr=spr, gtr=gtr,
+                      aa_model=aa_model, comm=comm, threads=threads, debug_flags=debug_flags, gamma=gamma, out_profile_parts=out_profile_parts, slow=slow,
+                      intree=intree, pseudo_weight=pseudo, ml_accuracy=ml_accuracy, slow_nni=slow_nni, nni_rounds=nni_rounds,
+                      ml_nni_rounds=ml_nni_rounds, spr_length=spr_length)
     blob = b"".join(nm.encode() + b"\0" for nm in names)
     cap = 64 * len(names) + len(blob) + 1024
     out = C.create_string_buffer(cap)
