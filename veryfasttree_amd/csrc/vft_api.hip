@@ -17,8 +17,8 @@
 
 #include "../../include/vft_hip.h"
 #include "vft_owned.h"
+#include "vft_staging.h"
 #define VFT_PAIR_STAGE_CAP 2048   // = the longest list the workgroup-per-pair kernels take
-#define VFT_SMALL_BYTES_ (256u << 10)   // = VFT_SMALL_BYTES below: what goes through the host-mapped ring
 #include "vft_kernels_ml.h"
 
 VFT_ML_HEAVY_INSTANCES(extern)   // compiled in vft_ml_kernels_*.hip
@@ -289,6 +289,7 @@ static int own_group(vft_ctx *c, F make) {
     do {                              \
         if (int r_ = (call)) return r_; \
     } while (0)
+#define VFTCHK(call) OWNCHK(call)   // ... of any call that returns a VFT_ code
 
 // a buffer that is replaced by a larger one when a request outgrows it (the stream may still be reading the old one)
 template <typename T>
@@ -491,6 +492,82 @@ static int io_alloc(vft_ctx *c, size_t bytes, char **host, char **dev) {
     return VFT_OK;
 }
 
+// two ranges of 16-byte pieces in one launch (host-mapped memory -> device memory)
+static __global__ void k_copy16x2(uint4 *dstA, const uint4 *srcA, int64_t nA, uint4 *dstB, const uint4 *srcB, int64_t nB) {
+    const int64_t t = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < nA) dstA[t] = srcA[t];
+    else if (t < nA + nB) dstB[t - nA] = srcB[t - nA];
+}
+
+// A call's arguments and results in one buffer laid out by a VftLayout (vft_staging.h): a slice of the host-mapped ring when the
+// layout fits the site's ring limit - inputs are written and results read in place, no staged copy - and the device scratch otherwise.
+struct Stage {
+    enum Wait { NO_WAIT, WAIT_STREAM, WAIT_FLAG };      // finish() on the ring path; the scratch path always synchronises the stream
+    static constexpr size_t RING_ONLY = ~(size_t) 0;   // a site without a scratch path: the ring refuses what it cannot hold
+    static constexpr size_t SCRATCH_ONLY = 0;          // a site whose arguments are always long (whole profiles)
+    vft_ctx *c = nullptr;
+    char *h = nullptr, *d = nullptr;   // host (ring path only) and device address of the layout's offset 0
+    bool ring = false;
+    struct Back {
+        void *dst;
+        size_t at, bytes;
+    } back[4];
+    int nBack = 0;
+
+    // total: the layout's total() (or the bytes of a single region at offset 0)
+    int open(vft_ctx *ctx, size_t total, size_t ringLimit) {
+        c = ctx;
+        ring = vft_takes_ring(total, ringLimit);
+        if (ring) return io_alloc(c, total, &h, &d);
+        if (int r = ensure_scratch(c, total)) return r;
+        d = (char *) c->scratch;
+        return VFT_OK;
+    }
+    template <typename T>
+    T *dev(size_t at) const { return (T *) (d + at); }
+    template <typename T>
+    T *host(size_t at) const { return (T *) (h + at); }   // ring path only: values that are composed in place
+    int put(size_t at, const void *src, size_t bytes) {
+        if (ring) memcpy(h + at, src, bytes);
+        else HIPCHK(c, hipMemcpyAsync(d + at, src, bytes, hipMemcpyHostToDevice, c->stream));
+        return VFT_OK;
+    }
+    // a result region for the caller (NULL: not wanted), delivered by finish()
+    void get(void *dst, size_t at, size_t bytes) {
+        if (dst) back[nBack++] = Back{dst, at, bytes};
+    }
+    // the call's wait.  Ring: for the flag a kernel raises with `seq`, for the stream, or none (inputs only: the ring's wrap-around
+    // protects them); then the results are copied out of the ring.  Scratch: result copies, then the stream (the inputs may be locals).
+    int finish(Wait w = NO_WAIT, unsigned long long seq = 0) {
+        if (int r = wait(w, seq)) return r;
+        return deliver();
+    }
+    // (its two halves, for a caller that times them)
+    int wait(Wait w, unsigned long long seq = 0) {
+        if (ring && w == WAIT_FLAG) return wait_flag(c, seq);
+        if (ring && w == WAIT_STREAM) return wait_stream(c);
+        return VFT_OK;
+    }
+    int deliver() {
+        if (ring) {
+            for (int k = 0; k < nBack; k++) memcpy(back[k].dst, h + back[k].at, back[k].bytes);
+            return VFT_OK;
+        }
+        for (int k = 0; k < nBack; k++)
+            HIPCHK(c, hipMemcpyAsync(back[k].dst, d + back[k].at, back[k].bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return VFT_OK;
+    }
+    // Second stage of the ring path: [atA, atA + bytesA) and [atB, atB + bytesB) of the ring, one behind the other, to device memory
+    // with 16-byte loads (bytes are rounded up to 16: the ring's slices and `dst` are 256-byte multiples).  A workgroup per item
+    // reading ITS ids from the ring is two 8-byte PCIe reads per item; the kernels then read device memory.
+    void to_device(void *dst, size_t atA, size_t bytesA, size_t atB = 0, size_t bytesB = 0) {
+        const int64_t nA = (int64_t) ((bytesA + 15) / 16), nB = (int64_t) ((bytesB + 15) / 16);
+        launch(k_copy16x2, dim3(cdiv(nA + nB, 256)), dim3(256), 0, c->stream, (uint4 *) dst, (const uint4 *) (d + atA), nA,
+               nB ? (uint4 *) ((char *) dst + bytesA) : (uint4 *) nullptr, nB ? (const uint4 *) (d + atB) : (const uint4 *) nullptr, nB);
+    }
+};
+
 
 static int raise_pair_kernel_lds(vft_ctx *c);   // defined next to the kernels it configures
 #define VFT_MAX_SLOTS 64                        // the seeds of the largest batch (vft_sweep_batch)
@@ -586,7 +663,7 @@ static int context_init(vft_ctx *c, const vft_config *cfg) {
     OWNCHK(own_host(c, &c->hFlag, &c->dFlag, 512, 512));
     OWNCHK(own_dev(c, &c->doneCtr, 65 * 4, 0));   // [0]: top level / single-level users, [1..64]: slots of vft_publish_staged
     OWNCHK(own_dev(c, &c->pairStage, 3 * VFT_PAIR_STAGE_CAP * sizeof(double)));   // staging of short pair lists' results (vft_publish_staged)
-    OWNCHK(own_dev(c, &c->pairIn, VFT_SMALL_BYTES_));   // device copy of a short list's inputs
+    OWNCHK(own_dev(c, &c->pairIn, VFT_SMALL_BYTES));   // device copy of a short list's inputs
     OWNCHK(own_host(c, &c->hIO, &c->dIO, c->ioCap, 0));
     OWNCHK(own_host(c, &c->hOutDist, &c->dOutDistM, (size_t) N * rs, (size_t) N * rs));
     OWNCHK(own_host(c, &c->hNOut, &c->dNOutM, (size_t) N * 4, (size_t) N * 4));
@@ -812,21 +889,19 @@ static int range_ok(vft_ctx *c, int64_t first, int64_t count) {
     return VFT_OK;
 }
 
-#define VFT_SMALL_BYTES (256u << 10)
-
 // dst[first .. first+count) = src (host), stream-ordered, no host synchronisation for small ranges
 template <typename T>
 static int store_range(vft_ctx *c, T *dst, T *mirror, const T *src, int64_t first, int64_t count) {
     const size_t bytes = (size_t) count * sizeof(T);
     if (bytes <= VFT_SMALL_BYTES) {
-        char *h, *d;
-        if (int r = io_alloc(c, bytes, &h, &d)) return r;
-        memcpy(h, src, bytes);
-        launch((k_store_range<T>), dim3(cdiv(count, 256)), dim3(256), 0, c->stream, dst, mirror, (const T *) d, first, count);
+        Stage st;
+        if (int r = st.open(c, bytes, Stage::RING_ONLY)) return r;
+        st.put(0, src, bytes);
+        launch((k_store_range<T>), dim3(cdiv(count, 256)), dim3(256), 0, c->stream, dst, mirror, st.dev<const T>(0), first, count);
         LAUNCHCHK(c);
         return VFT_OK;
     }
-    HIPCHK(c, hipMemcpyAsync(dst + first, src, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst + first, src, bytes, hipMemcpyHostToDevice, c->stream));   // (straight to its place: no scratch)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return VFT_OK;
 }
@@ -977,8 +1052,8 @@ static CommitPlan commit_plan(const vft_ctx *c, int64_t n) {
     int64_t chunk = (int64_t) ((256u << 20) / perNode);
     chunk = chunk < 64 ? 64 : chunk > 16384 ? 16384 : chunk;
     p.chunk = n < chunk ? (n > 0 ? n : 1) : chunk;
-    p.stashB = (((size_t) p.chunk * perNode) + 255) & ~(size_t) 255;
-    p.metaB = (((size_t) (2 * p.chunk + 2) * 4) + 255) & ~(size_t) 255;
+    p.stashB = vft_pad256((size_t) p.chunk * perNode);
+    p.metaB = vft_pad256((size_t) (2 * p.chunk + 2) * 4);
     p.stride = vft_commit_scratch_bytes(c->d, c->rs);
     const int64_t segs = p.chunk < VFT_COMMIT_SEGS ? p.chunk : VFT_COMMIT_SEGS;
     p.totalB = p.stashB + p.metaB + (size_t) segs * p.stride;
@@ -1031,16 +1106,15 @@ static int commit_nodes(vft_ctx *c, const CommitPlan &plan, const int64_t *hNode
     const int64_t nSeg = (int64_t) segFirst.size() - 1;
     meta.insert(meta.end(), segFirst.begin(), segFirst.end());
     const size_t bytes = meta.size() * 4;
-    char *dMeta;
-    bool viaScratch = false;
-    if (bytes <= VFT_SMALL_BYTES) {
-        char *h;
-        if (int r = io_alloc(c, bytes, &h, &dMeta)) return r;
-        memcpy(h, meta.data(), bytes);
+    const char *dMeta = base + plan.stashB;   // the plan's own meta region when the ring does not take them
+    const bool viaScratch = !vft_takes_ring(bytes, VFT_SMALL_BYTES);
+    if (viaScratch) {
+        HIPCHK(c, hipMemcpyAsync(base + plan.stashB, meta.data(), bytes, hipMemcpyHostToDevice, c->stream));
     } else {
-        dMeta = base + plan.stashB;
-        HIPCHK(c, hipMemcpyAsync(dMeta, meta.data(), bytes, hipMemcpyHostToDevice, c->stream));
-        viaScratch = true;
+        Stage st;
+        if (int r = st.open(c, bytes, VFT_SMALL_BYTES)) return r;
+        st.put(0, meta.data(), bytes);
+        dMeta = st.dev<const char>(0);
     }
     const int32_t *dOrder = (const int32_t *) dMeta, *dSeg = dOrder + cnt;
     char *cs = base + plan.stashB + plan.metaB;
@@ -1080,24 +1154,22 @@ extern "C" int vft_profile_upload(vft_ctx *c, int64_t node, const void *w, const
     if (int r = internal_ok(c, node)) return r;
     const VftDims &d = c->d;
     const size_t rs = c->rs, wB = d.nPos * rs, fB = d.nPos * d.nCodes * rs, cB = (size_t) d.nPos;
-    const size_t inB = (wB + fB + cB + 255) & ~(size_t) 255;
     const CommitPlan plan = commit_plan(c, 1);
-    if (int r = ensure_scratch(c, inB + plan.totalB + 256)) return r;
-    char *s = (char *) c->scratch;
-    char *base = s + inB;
-    HIPCHK(c, hipMemcpyAsync(s, w, wB, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(s + wB, f, fB, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(s + wB + fB, codes, cB, hipMemcpyHostToDevice, c->stream));
-    char *hId, *dId;
-    if (int r = io_alloc(c, 8, &hId, &dId)) return r;
-    memcpy(hId, &node, 8);
-    VFT_DISPATCH(c, (launch((k_profile_scatter<REAL, NC>), dim3(cdiv(d.nPos, 256)), dim3(256), 0, c->stream,
-                                        arena<REAL>(c), node, (const REAL *) s, (const uint8_t *) (s + wB + fB),
-                                        (const REAL *) (s + wB), (REAL *) base)));
+    VftLayout L;
+    const size_t oW = L.add(wB), oF = L.add(fB), oC = L.add(cB), oBase = L.add(plan.totalB, 256);
+    Stage st, id;
+    if (int r = st.open(c, L.total(), Stage::SCRATCH_ONLY)) return r;
+    if (int r = id.open(c, 8, Stage::RING_ONLY)) return r;
+    VFTCHK(st.put(oW, w, wB));
+    VFTCHK(st.put(oF, f, fB));
+    VFTCHK(st.put(oC, codes, cB));
+    id.put(0, &node, 8);
+    char *base = st.dev<char>(oBase);
+    VFT_DISPATCH(c, (launch((k_profile_scatter<REAL, NC>), dim3(cdiv(d.nPos, 256)), dim3(256), 0, c->stream, arena<REAL>(c), node,
+                            st.dev<const REAL>(oW), st.dev<const uint8_t>(oC), st.dev<const REAL>(oF), (REAL *) base)));
     LAUNCHCHK(c);
-    if (int r = commit_nodes(c, plan, &node, (const int64_t *) dId, 1, base)) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VFT_OK;
+    if (int r = commit_nodes(c, plan, &node, id.dev<const int64_t>(0), 1, base)) return r;
+    return st.finish();
 }
 
 extern "C" int vft_profile_download(vft_ctx *c, int64_t node, void *w, uint8_t *codes, void *f) {
@@ -1105,16 +1177,17 @@ extern "C" int vft_profile_download(vft_ctx *c, int64_t node, void *w, uint8_t *
     if (node < 0 || node >= c->d.maxNodes) return fail(c, VFT_ERR_INVALID, "bad node");
     const VftDims &d = c->d;
     const size_t rs = c->rs, wB = d.nPos * rs, fB = d.nPos * d.nCodes * rs, cB = (size_t) d.nPos;
-    if (int r = ensure_scratch(c, wB + fB + cB + 64)) return r;
-    char *s = (char *) c->scratch;
-    VFT_DISPATCH(c, (launch((k_profile_gather<REAL, NC>), dim3(cdiv(d.nPos, 256)), dim3(256), 0, c->stream,
-                                        arena<REAL>(c), node, (REAL *) s, (uint8_t *) (s + wB + fB), (REAL *) (s + wB))));
+    VftLayout L;
+    const size_t oW = L.add(wB), oF = L.add(fB), oC = L.add(cB);
+    Stage st;
+    if (int r = st.open(c, L.total(), Stage::SCRATCH_ONLY)) return r;
+    VFT_DISPATCH(c, (launch((k_profile_gather<REAL, NC>), dim3(cdiv(d.nPos, 256)), dim3(256), 0, c->stream, arena<REAL>(c), node,
+                            st.dev<REAL>(oW), st.dev<uint8_t>(oC), st.dev<REAL>(oF))));
     LAUNCHCHK(c);
-    HIPCHK(c, hipMemcpyAsync(w, s, wB, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(f, s + wB, fB, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(codes, s + wB + fB, cB, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VFT_OK;
+    st.get(w, oW, wB);
+    st.get(f, oF, fB);
+    st.get(codes, oC, cB);
+    return st.finish();
 }
 
 template <typename REAL, int NC>
@@ -1138,13 +1211,13 @@ extern "C" int vft_profile_nvectors(vft_ctx *c, int64_t first, int64_t count, in
     if (first < 0 || count < 0 || first + count > c->d.maxNodes) return fail(c, VFT_ERR_INVALID, "node range out of bounds");
     if (count == 0) return VFT_OK;
     if (int r = flush_pending(c)) return r;
-    if (int r = ensure_scratch(c, (size_t) count * 8)) return r;
+    Stage st;
+    if (int r = st.open(c, (size_t) count * 8, Stage::SCRATCH_ONLY)) return r;
     VFT_DISPATCH(c, launch((k_nvectors<REAL, NC>), dim3(cdiv(count, 64)), dim3(64), 0, c->stream, arena<REAL>(c), first, count,
-                           (int64_t *) c->scratch));
+                           st.dev<int64_t>(0)));
     LAUNCHCHK(c);
-    HIPCHK(c, hipMemcpyAsync(nvec, c->scratch, (size_t) count * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VFT_OK;
+    st.get(nvec, 0, (size_t) count * 8);
+    return st.finish();
 }
 
 template <typename REAL, int NC>
@@ -1226,55 +1299,58 @@ extern "C" int vft_average_profiles(vft_ctx *c, int64_t n, const int64_t *out, c
         plan.totalB = 0;
     }
     const int64_t chunk = plan.chunk;
-    const size_t idB = (((size_t) n * 8) + 255) & ~(size_t) 255;
-    const bool smallIds = 4 * idB <= VFT_SMALL_BYTES;
-    if (int r = ensure_scratch(c, (smallIds ? 0 : 4 * idB) + plan.totalB + 512)) return r;
-    char *s, *base;
-    if (smallIds) {
-        char *h;
-        if (int r = io_alloc(c, 4 * idB, &h, &s)) return r;
-        memcpy(h, out, (size_t) n * 8);
-        memcpy(h + idB, a, (size_t) n * 8);
-        memcpy(h + 2 * idB, b, (size_t) n * 8);
-        if (bionj) memcpy(h + 3 * idB, bionj, (size_t) n * 8);
-        base = (char *) c->scratch;
-    } else {
-        s = (char *) c->scratch;
-        base = s + 4 * idB;
-        HIPCHK(c, hipMemcpyAsync(s, out, (size_t) n * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(s + idB, a, (size_t) n * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(s + 2 * idB, b, (size_t) n * 8, hipMemcpyHostToDevice, c->stream));
-        if (bionj) HIPCHK(c, hipMemcpyAsync(s + 3 * idB, bionj, (size_t) n * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    base += (256 - ((uintptr_t) base & 255)) & 255;
+    const size_t idB = (size_t) n * 8;
+    VftLayout L;   // the four lists (ring or scratch); the commit plan's block is scratch on either path
+    const size_t oOut = L.add(idB, 256), oA = L.add(idB, 256), oB = L.add(idB, 256), oBionj = L.add(idB, 256);
+    const size_t oEnd = L.add(0, 256);
+    const bool smallIds = vft_takes_ring(L.total(), VFT_SMALL_BYTES);
+    if (int r = ensure_scratch(c, (smallIds ? 0 : oEnd) + plan.totalB)) return r;
+    Stage st;
+    if (int r = st.open(c, L.total(), VFT_SMALL_BYTES)) return r;
+    VFTCHK(st.put(oOut, out, idB));
+    VFTCHK(st.put(oA, a, idB));
+    VFTCHK(st.put(oB, b, idB));
+    if (bionj) VFTCHK(st.put(oBionj, bionj, idB));
+    char *base = (char *) c->scratch + (smallIds ? 0 : oEnd);
+    const int64_t *dOut = st.dev<const int64_t>(oOut);
     for (int64_t k0 = 0; k0 < n; k0 += chunk) {
         const int64_t cnt = n - k0 < chunk ? n - k0 : chunk;
         VFT_DISPATCH(c, {
             const dim3 grid(cdiv(c->d.nPos, 128), (unsigned) cnt);
-            launch((k_average<REAL, NC>), grid, dim3(128), 0, c->stream, arena<REAL>(c), (const int64_t *) s + k0,
-                   (const int64_t *) (s + idB) + k0, (const int64_t *) (s + 2 * idB) + k0,
-                   bionj ? (const double *) (s + 3 * idB) + k0 : (const double *) nullptr, c->fpostTol,
+            launch((k_average<REAL, NC>), grid, dim3(128), 0, c->stream, arena<REAL>(c), dOut + k0, st.dev<const int64_t>(oA) + k0,
+                   st.dev<const int64_t>(oB) + k0, bionj ? st.dev<const double>(oBionj) + k0 : (const double *) nullptr, c->fpostTol,
                    rows ? (REAL *) nullptr : (REAL *) base);
         });
         LAUNCHCHK(c);
         if (!rows)
-            if (int r = commit_nodes(c, plan, out + k0, (const int64_t *) s + k0, cnt, base)) return r;
+            if (int r = commit_nodes(c, plan, out + k0, dOut + k0, cnt, base)) return r;
     }
-    if (rows) {
-        if (!smallIds) HIPCHK(c, hipStreamSynchronize(c->stream));
-        return VFT_OK;
-    }
+    if (rows) return st.finish();
     if (n == 1) {
         VFT_DISPATCH(c, launch((k_selfdist_one<REAL, NC>), dim3(1), dim3(VFT_WG), pw_lds_bytes(c) / c->pwWaves, c->stream,
-                               arena<REAL>(c), (const int64_t *) s));
+                               arena<REAL>(c), dOut));
     } else {
         VFT_DISPATCH(c, launch((k_selfdist<REAL, NC>), dim3(cdiv(n, c->pwWaves)), dim3(64 * c->pwWaves), pw_lds_bytes(c), c->stream,
-                               arena<REAL>(c), (const int64_t *) s, n));
+                               arena<REAL>(c), dOut, n));
     }
     LAUNCHCHK(c);
-    // id lists in the mapped ring are protected by its wrap-around synchronisation; only the scratch path must wait
-    if (!smallIds) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VFT_OK;
+    return st.finish();
+}
+
+// direct[k] of a chain's op k: bit 0 / bit 1 when child a / b is the output of an earlier op of the same chain
+static void chain_direct_flags(uint8_t *direct, int32_t nChains, const int32_t *chainOff, int32_t n, const int64_t *out, const int64_t *a,
+                               const int64_t *b) {
+    for (int32_t ch = 0; ch < nChains; ch++) {
+        const int32_t k0 = chainOff ? chainOff[ch] : 0, k1 = chainOff ? chainOff[ch + 1] : n;
+        for (int32_t k = k0; k < k1; k++) {
+            uint8_t d = 0;
+            for (int32_t j = k0; j < k; j++) {
+                if (out[j] == a[k]) d |= 1;
+                if (out[j] == b[k]) d |= 2;
+            }
+            direct[k] = d;
+        }
+    }
 }
 
 // n unweighted averages in order, later ones may read earlier results (k_average_chain); profile-rows mode only.
@@ -1288,29 +1364,20 @@ static int average_chains(vft_ctx *c, int32_t nChains, const int32_t *chainOff, 
         if (a[k] < 0 || a[k] >= c->d.maxNodes || b[k] < 0 || b[k] >= c->d.maxNodes) return fail(c, VFT_ERR_INVALID, "bad child id");
     }
     if (int r = ensure_ml_rows(c)) return r;
-    const size_t idB = (size_t) n * 8, dB = ((size_t) n + 7) & ~(size_t) 7, offB = chainOff ? (size_t) (nChains + 1) * 4 : 0;
-    char *h, *s;
-    if (int r = io_alloc(c, 3 * idB + dB + offB, &h, &s)) return r;
-    memcpy(h, out, idB);
-    memcpy(h + idB, a, idB);
-    memcpy(h + 2 * idB, b, idB);
-    uint8_t *direct = (uint8_t *) (h + 3 * idB);
-    for (int32_t ch = 0; ch < nChains; ch++) {
-        const int32_t k0 = chainOff ? chainOff[ch] : 0, k1 = chainOff ? chainOff[ch + 1] : n;
-        for (int32_t k = k0; k < k1; k++) {
-            uint8_t d = 0;
-            for (int32_t j = k0; j < k; j++) {
-                if (out[j] == a[k]) d |= 1;
-                if (out[j] == b[k]) d |= 2;
-            }
-            direct[k] = d;
-        }
-    }
-    if (chainOff) memcpy(h + 3 * idB + dB, chainOff, offB);
+    const size_t idB = (size_t) n * 8, offB = chainOff ? (size_t) (nChains + 1) * 4 : 0;
+    VftLayout L;
+    const size_t oOut = L.add(idB), oA = L.add(idB), oB = L.add(idB), oDirect = L.add((size_t) n), oOff = L.add(offB, 8);
+    Stage st;
+    if (int r = st.open(c, L.total(), Stage::RING_ONLY)) return r;
+    st.put(oOut, out, idB);
+    st.put(oA, a, idB);
+    st.put(oB, b, idB);
+    chain_direct_flags(st.host<uint8_t>(oDirect), nChains, chainOff, n, out, a, b);
+    if (chainOff) st.put(oOff, chainOff, offB);
     VFT_DISPATCH(c, launch((k_average_chain<REAL, NC>), dim3(cdiv(c->d.nPos, 128), (unsigned) nChains), dim3(128), 0, c->stream, arena<REAL>(c),
-                           (const int64_t *) s, (const int64_t *) (s + idB), (const int64_t *) (s + 2 * idB),
-                           (const uint8_t *) (s + 3 * idB), n, c->fpostTol, chainOff ? (const int32_t *) (s + 3 * idB + dB) : nullptr));
-    if (!c->allRows) launch(k_mark_rows, dim3(cdiv(n, 64)), dim3(64), 0, c->stream, c->mlIs, (const int64_t *) s, n, c->d.nSeqs);
+                           st.dev<const int64_t>(oOut), st.dev<const int64_t>(oA), st.dev<const int64_t>(oB), st.dev<const uint8_t>(oDirect), n,
+                           c->fpostTol, chainOff ? st.dev<const int32_t>(oOff) : nullptr));
+    if (!c->allRows) launch(k_mark_rows, dim3(cdiv(n, 64)), dim3(64), 0, c->stream, c->mlIs, st.dev<const int64_t>(oOut), n, c->d.nSeqs);
     LAUNCHCHK(c);
     return VFT_OK;
 }
@@ -1665,18 +1732,19 @@ extern "C" int vft_profiles_differ(vft_ctx *c, int64_t n, const int64_t *a, cons
     if (n > 4096) return fail(c, VFT_ERR_INVALID, "vft_profiles_differ: at most 4096 pairs per call");
     for (int64_t k = 0; k < n; k++)
         if (a[k] < 0 || a[k] >= c->maxnode || b[k] < 0 || b[k] >= c->maxnode) return fail(c, VFT_ERR_INVALID, "vft_profiles_differ: pair %lld out of range", (long long) k);
-    const size_t idB = (size_t) n * 8, flB = ((size_t) n * 4 + 255) & ~(size_t) 255;
-    char *h, *s;
-    if (int r = io_alloc(c, 2 * idB + flB, &h, &s)) return r;
-    memcpy(h, a, idB);
-    memcpy(h + idB, b, idB);
-    memset(h + 2 * idB, 0, flB);
+    const size_t idB = (size_t) n * 8, flB = (size_t) n * 4;
+    VftLayout L;
+    const size_t oA = L.add(idB), oB = L.add(idB), oFlag = L.add(flB);
+    Stage st;
+    if (int r = st.open(c, L.total(), Stage::RING_ONLY)) return r;
+    st.put(oA, a, idB);
+    st.put(oB, b, idB);
+    memset(st.host<char>(oFlag), 0, flB);
     VFT_DISPATCH(c, launch((k_rows_differ<REAL, NC>), dim3(cdiv(c->d.nPos, 128), (unsigned) n), dim3(128), 0, c->stream, arena<REAL>(c),
-                           (const int64_t *) s, (const int64_t *) (s + idB), (int32_t *) (s + 2 * idB)));
+                           st.dev<const int64_t>(oA), st.dev<const int64_t>(oB), st.dev<int32_t>(oFlag)));
     LAUNCHCHK(c);
-    if (int w = wait_stream(c)) return w;
-    memcpy(differ, h + 2 * idB, (size_t) n * 4);
-    return VFT_OK;
+    st.get(differ, oFlag, flB);
+    return st.finish(Stage::WAIT_STREAM);
 }
 
 extern "C" int vft_get_n_codes(vft_ctx *c, int32_t *nCodes) {
@@ -1785,13 +1853,13 @@ extern "C" int vft_out_profile_full(vft_ctx *c, int64_t n, const int64_t *ids) {
     }
     for (int64_t k = 0; k < n; k++)
         if (ids[k] < 0 || ids[k] >= c->maxnode) return fail(c, VFT_ERR_INVALID, "vft_out_profile_full: node %lld out of range", (long long) ids[k]);
-    if (int r = ensure_scratch(c, (size_t) n * 8)) return r;
-    HIPCHK(c, hipMemcpyAsync(c->scratch, ids, (size_t) n * 8, hipMemcpyHostToDevice, c->stream));
+    Stage st;
+    if (int r = st.open(c, (size_t) n * 8, Stage::SCRATCH_ONLY)) return r;
+    VFTCHK(st.put(0, ids, (size_t) n * 8));
     VFT_DISPATCH(c, (launch((k_outprofile_full<REAL, NC>), dim3(cdiv(c->d.nPos, 64)), dim3(64), 0, c->stream,
-                                        arena<REAL>(c), (const int64_t *) c->scratch, n, c->fpostTol)));
+                                        arena<REAL>(c), st.dev<const int64_t>(0), n, c->fpostTol)));
     LAUNCHCHK(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VFT_OK;
+    return st.finish();
 }
 
 // outProfile in parts (vft_kernels_profile.h: k_outprofile_partial / k_outprofile_finish).  vft_out_profile_partial: the raw sums of
@@ -1803,27 +1871,28 @@ extern "C" int vft_out_profile_partial(vft_ctx *c, int64_t nTotal, int64_t n, co
     for (int64_t k = 0; k < n; k++)
         if (ids[k] < 0 || ids[k] >= c->maxnode) return fail(c, VFT_ERR_INVALID, "vft_out_profile_partial: node %lld out of range", (long long) ids[k]);
     const size_t pb = (size_t) c->d.nPos * (size_t) (1 + c->d.nCodes) * c->rs;
-    if (int r = ensure_scratch(c, (size_t) (n > 0 ? n : 1) * 8 + pb + 64)) return r;
-    char *dIds = (char *) c->scratch, *dPart = dIds + (((size_t) (n > 0 ? n : 1) * 8 + 63) / 64) * 64;
-    if (n > 0) HIPCHK(c, hipMemcpyAsync(dIds, ids, (size_t) n * 8, hipMemcpyHostToDevice, c->stream));
+    VftLayout L;
+    const size_t oIds = L.add((size_t) (n > 0 ? n : 1) * 8), oPart = L.add(pb, 64);
+    Stage st;
+    if (int r = st.open(c, L.total(), Stage::SCRATCH_ONLY)) return r;
+    if (n > 0) VFTCHK(st.put(oIds, ids, (size_t) n * 8));
     VFT_DISPATCH(c, (launch((k_outprofile_partial<REAL, NC>), dim3(cdiv(c->d.nPos, 64)), dim3(64), 0, c->stream,
-                            arena<REAL>(c), (const int64_t *) dIds, n, nTotal, (REAL *) dPart)));
+                            arena<REAL>(c), st.dev<const int64_t>(oIds), n, nTotal, st.dev<REAL>(oPart))));
     LAUNCHCHK(c);
-    HIPCHK(c, hipMemcpyAsync(part, dPart, pb, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VFT_OK;
+    st.get(part, oPart, pb);
+    return st.finish();
 }
 
 extern "C" int vft_out_profile_finish(vft_ctx *c, int32_t nParts, const void *parts) {
     if (!c || nParts < 1 || !parts) return VFT_ERR_INVALID;
     const size_t pb = (size_t) c->d.nPos * (size_t) (1 + c->d.nCodes) * c->rs;
-    if (int r = ensure_scratch(c, (size_t) nParts * pb)) return r;
-    HIPCHK(c, hipMemcpyAsync(c->scratch, parts, (size_t) nParts * pb, hipMemcpyHostToDevice, c->stream));
+    Stage st;
+    if (int r = st.open(c, (size_t) nParts * pb, Stage::SCRATCH_ONLY)) return r;
+    VFTCHK(st.put(0, parts, (size_t) nParts * pb));
     VFT_DISPATCH(c, (launch((k_outprofile_finish<REAL, NC>), dim3(cdiv(c->d.nPos, 64)), dim3(64), 0, c->stream,
-                            arena<REAL>(c), (const REAL *) c->scratch, nParts, c->fpostTol)));
+                            arena<REAL>(c), st.dev<const REAL>(0), nParts, c->fpostTol)));
     LAUNCHCHK(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // (the scratch block may be reused by the next call)
-    return VFT_OK;
+    return st.finish();
 }
 
 extern "C" int vft_out_profile_update(vft_ctx *c, int64_t old1, int64_t old2, int64_t newn, int64_t nActiveOld) {
@@ -1980,17 +2049,11 @@ extern "C" int vft_out_distances(vft_ctx *c, int64_t n, const int64_t *ids, int6
             LAUNCHCHK(c);
             return VFT_OK;
         }
-        char *h, *d;
-        if ((size_t) n * 8 <= VFT_SMALL_BYTES) {
-            if (int r = io_alloc(c, (size_t) n * 8, &h, &d)) return r;
-            memcpy(h, ids, (size_t) n * 8);
-            return launch_out_distances(c, (const int64_t *) d, n, nActive, 0, totdiam, true);
-        }
-        if (int r = ensure_scratch(c, (size_t) n * 8)) return r;
-        HIPCHK(c, hipMemcpyAsync(c->scratch, ids, (size_t) n * 8, hipMemcpyHostToDevice, c->stream));
-        if (int r = launch_out_distances(c, (const int64_t *) c->scratch, n, nActive, 0, totdiam, true)) return r;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return VFT_OK;
+        Stage st;
+        if (int r = st.open(c, (size_t) n * 8, VFT_SMALL_BYTES)) return r;
+        VFTCHK(st.put(0, ids, (size_t) n * 8));
+        if (int r = launch_out_distances(c, st.dev<const int64_t>(0), n, nActive, 0, totdiam, true)) return r;
+        return st.finish();
     }
     return launch_out_distances(c, nullptr, 0, nActive, 0, totdiam, true);
 }
@@ -2112,10 +2175,10 @@ static int run_select(vft_ctx *c, int K, const int64_t *queries, int64_t lo, int
         d.nPart = h.nPart;
         d.pad = 0;
     }
-    char *hS, *dS;
-    if (int r = io_alloc(c, hs.size() * sizeof(SelSlot), &hS, &dS)) return r;
-    memcpy(hS, hs.data(), hs.size() * sizeof(SelSlot));
-    const SelSlot *slots = (const SelSlot *) dS;
+    Stage st;
+    if (int r = st.open(c, hs.size() * sizeof(SelSlot), Stage::RING_ONLY)) return r;
+    st.put(0, hs.data(), hs.size() * sizeof(SelSlot));
+    const SelSlot *slots = st.dev<const SelSlot>(0);
     // hist (round one: with the key range) -> collect (every workgroup finds the threshold digit in the seed's histogram itself) -> rank; the rank sort's last workgroup of every seed finishes the
     // selection and writes `seq` into the seed's host header - the host waits for those words, no kernel behind the rank sort
     auto round = [&](const SelSlot *sl, unsigned ny, int first, int s0) -> int {
@@ -2396,9 +2459,9 @@ extern "C" int vft_sweep_batch(vft_ctx *c, int32_t nSeeds, const int64_t *querie
                     mqIdx[(size_t) groups[g].pos[q]] = q;
                     mqS[(size_t) groups[g].pos[q]] = groups[g].n;
                 }
-        char *hQ, *dQ;
+        Stage st;
+        if (int r = st.open(c, (size_t) nSeeds * (c->cfg.precision == 4 ? sizeof(QuerySlot<float>) : sizeof(QuerySlot<double>)), Stage::RING_ONLY)) return r;
         if (c->cfg.precision == 4) {
-            if (int r = io_alloc(c, (size_t) nSeeds * sizeof(QuerySlot<float>), &hQ, &dQ)) return r;
             for (int s = 0; s < nSeeds; s++) {
                 QuerySlot<float> qs;
                 qs.node = queries[s];
@@ -2406,11 +2469,10 @@ extern "C" int vft_sweep_batch(vft_ctx *c, int32_t nSeeds, const int64_t *querie
                 qs.mq = mqGroup[(size_t) s] >= 0 ? (float *) ((char *) c->mqBuf + (size_t) mqGroup[(size_t) s] * c->mqGroupBytes) : nullptr;
                 qs.mqIdx = mqIdx[(size_t) s];
                 qs.mqS = mqS[(size_t) s];
-                memcpy(hQ + (size_t) s * sizeof(qs), &qs, sizeof(qs));
+                st.put((size_t) s * sizeof(qs), &qs, sizeof(qs));
             }
-            launch((k_extract_query_batch<float, 4>), dim3(cdiv(nPosPad, 256), (unsigned) nSeeds), dim3(256), 0, c->stream, arena<float>(c), (const QuerySlot<float> *) dQ);
+            launch((k_extract_query_batch<float, 4>), dim3(cdiv(nPosPad, 256), (unsigned) nSeeds), dim3(256), 0, c->stream, arena<float>(c), st.dev<const QuerySlot<float>>(0));
         } else {
-            if (int r = io_alloc(c, (size_t) nSeeds * sizeof(QuerySlot<double>), &hQ, &dQ)) return r;
             for (int s = 0; s < nSeeds; s++) {
                 QuerySlot<double> qs;
                 qs.node = queries[s];
@@ -2418,9 +2480,9 @@ extern "C" int vft_sweep_batch(vft_ctx *c, int32_t nSeeds, const int64_t *querie
                 qs.mq = mqGroup[(size_t) s] >= 0 ? (double *) ((char *) c->mqBuf + (size_t) mqGroup[(size_t) s] * c->mqGroupBytes) : nullptr;
                 qs.mqIdx = mqIdx[(size_t) s];
                 qs.mqS = mqS[(size_t) s];
-                memcpy(hQ + (size_t) s * sizeof(qs), &qs, sizeof(qs));
+                st.put((size_t) s * sizeof(qs), &qs, sizeof(qs));
             }
-            launch((k_extract_query_batch<double, 4>), dim3(cdiv(nPosPad, 256), (unsigned) nSeeds), dim3(256), 0, c->stream, arena<double>(c), (const QuerySlot<double> *) dQ);
+            launch((k_extract_query_batch<double, 4>), dim3(cdiv(nPosPad, 256), (unsigned) nSeeds), dim3(256), 0, c->stream, arena<double>(c), st.dev<const QuerySlot<double>>(0));
         }
         LAUNCHCHK(c);
     }
@@ -2565,13 +2627,6 @@ extern "C" int vft_sweep_results(vft_ctx *c, int64_t first, int64_t count, void 
     return VFT_OK;
 }
 
-// two ranges of 16-byte pieces in one launch (host-mapped memory -> device memory)
-static __global__ void k_copy16x2(uint4 *dstA, const uint4 *srcA, int64_t nA, uint4 *dstB, const uint4 *srcB, int64_t nB) {
-    const int64_t t = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (t < nA) dstA[t] = srcA[t];
-    else if (t < nA + nB) dstB[t - nA] = srcB[t - nA];
-}
-
 static int pair_distances(vft_ctx *c, int64_t n, const int64_t *pi, const int64_t *pj, int64_t nActive, int64_t nDiffAllow,
                           double totdiam, void *dist, void *weight, void *crit, bool raw, int64_t nForce, const int64_t *forceIds);
 extern "C" int vft_pair_distances(vft_ctx *c, int64_t n, const int64_t *pi, const int64_t *pj, int64_t nActive,
@@ -2602,101 +2657,62 @@ static int pair_distances(vft_ctx *c, int64_t n, const int64_t *pi, const int64_
     if (!c->leavesUp) return fail(c, VFT_ERR_STATE, "vft_pair_distances before vft_upload_leaves");
     for (int64_t t = 0; t < n; t++)
         if (pi[t] < 0 || pi[t] >= c->maxnode || pj[t] < 0 || pj[t] >= c->maxnode) return fail(c, VFT_ERR_INVALID, "pair %lld out of range", (long long) t);
-    const size_t rs = c->rs, idB = (((size_t) n * 8) + 255) & ~(size_t) 255, oB = (((size_t) n * rs) + 255) & ~(size_t) 255;
-    // setCriterion's lazy refresh (NJ.tcc:1092-1098) for the nodes the list names: the DISTINCT stale ones, found on the
-    // host-mapped stamp mirror (it can only lag towards "staler": kernels in flight make nodes fresher, host-side sets
-    // update it at once; the kernel looks at the real stamp again).  A node is typically named by hundreds of pairs
+    const size_t rs = c->rs, idB = (size_t) n * 8, resB = (size_t) n * rs;
+    // setCriterion's lazy refresh (vft_staging.h) for the nodes the list names.  A node is typically named by hundreds of pairs
     // (the new node of a join by all of its candidates): one workgroup / wave per NAME recomputed the same value that
     // many times - 0.85 ms of a 0.94 ms call at 60 000 pairs.
     std::vector<int64_t> &stale = c->staleIds;
     stale.clear();
     int64_t nForced = 0;
+    VftStaleSet set(c->hNOut, c->staleMark, c->staleEpoch, (size_t) c->d.maxNodes, nActive, nDiffAllow, stale, &c->staleIdx);
     if (!raw) {
-        if (c->staleMark.size() != (size_t) c->d.maxNodes) c->staleMark.assign((size_t) c->d.maxNodes, 0u);
-        if (++c->staleEpoch == 0u) {
-            std::fill(c->staleMark.begin(), c->staleMark.end(), 0u);
-            c->staleEpoch = 1u;
-        }
-        const uint32_t ep = c->staleEpoch;
-        uint32_t *mark = c->staleMark.data();
         // forced refreshes first (setOutDistance, NJ.tcc:1012-1015: recomputed unless the stamp IS n_active); the kernel
         // applies that rule to the first nForced entries of the list and the lazy one to the rest
-        if (c->staleIdx.size() != (size_t) c->d.maxNodes) c->staleIdx.assign((size_t) c->d.maxNodes, -1);
-        int32_t *sidx = c->staleIdx.data();   // position in the list, valid where mark == ep
-        for (int64_t t = 0; t < nForce; t++) {
-            const int64_t v = forceIds[t];
-            if ((int64_t) c->hNOut[v] != nActive && mark[v] != ep) {
-                mark[v] = ep;
-                sidx[v] = (int32_t) stale.size();
-                stale.push_back(v);
-            }
-        }
+        set.add(forceIds, nForce, true);
         nForced = (int64_t) stale.size();
         for (int64_t t = 0; t < n; t++) {
-            const int64_t a = pi[t], b = pj[t];
-            if ((int64_t) c->hNOut[a] - nActive > nDiffAllow && mark[a] != ep) {
-                mark[a] = ep;
-                sidx[a] = (int32_t) stale.size();
-                stale.push_back(a);
-            }
-            if ((int64_t) c->hNOut[b] - nActive > nDiffAllow && mark[b] != ep) {
-                mark[b] = ep;
-                sidx[b] = (int32_t) stale.size();
-                stale.push_back(b);
-            }
+            set.add(pi[t]);
+            set.add(pj[t]);
         }
     }
     const int64_t nStale = (int64_t) stale.size();
-    const size_t sB = (((size_t) nStale * 8) + 255) & ~(size_t) 255;
-    const size_t wB = (((size_t) n * 8) + 255) & ~(size_t) 255;   // per-pair wait indices of the single-launch variant
-    const bool small = 2 * idB + 3 * oB + sB + wB <= VFT_SMALL_BYTES;
+    VftLayout L;   // every region a multiple of 256 bytes: the copy stage below moves whole 16-byte pieces
+    const size_t oI = L.add(idB, 256), oJ = L.add(idB, 256), oDist = L.add(resB, 256), oWeight = L.add(resB, 256), oCrit = L.add(resB, 256);
+    const size_t oStale = L.add((size_t) nStale * 8, 256);
+    const size_t oWait = L.add(idB, 256);   // per-pair wait indices of the single-launch variant
+    const size_t oEnd = L.add(0, 256);
+    const bool small = vft_takes_ring(L.total(), VFT_SMALL_BYTES);
     // (the pair workgroups of the single-launch variant spin on tags of refresh workgroups of the same grid: only while the
     //  whole grid is resident at once, whatever order the dispatcher picks)
     bool fusedRefresh = small && nStale > 0 && n <= 2048 && n + nStale <= c->fusedLimit && !c->noFusedRefresh;
     if (fusedRefresh && !c->refDone) {
         OWNCHK(own_dev(c, &c->refDone, 4096 * sizeof(unsigned int), 0, ON_STREAM));
     }
-    char *hBase = nullptr, *dBase = nullptr;
-    if (small) {
-        if (int r = io_alloc(c, 2 * idB + 3 * oB + sB + wB, &hBase, &dBase)) return r;
-        memcpy(hBase, pi, (size_t) n * 8);
-        memcpy(hBase + idB, pj, (size_t) n * 8);
-        if (nStale) memcpy(hBase + 2 * idB + 3 * oB, stale.data(), (size_t) nStale * 8);
-        if (fusedRefresh) {   // which refresh workgroup each end of a pair has to wait for (-1: none)
-            int32_t *wt = (int32_t *) (hBase + 2 * idB + 3 * oB + sB);
-            const uint32_t ep = c->staleEpoch;
-            const uint32_t *mark = c->staleMark.data();
-            const int32_t *sidx = c->staleIdx.data();
-            for (int64_t t = 0; t < n; t++) {
-                wt[2 * t] = mark[pi[t]] == ep ? sidx[pi[t]] : -1;
-                wt[2 * t + 1] = mark[pj[t]] == ep ? sidx[pj[t]] : -1;
-            }
+    Stage st;
+    if (int r = st.open(c, L.total(), VFT_SMALL_BYTES)) return r;
+    VFTCHK(st.put(oI, pi, idB));
+    VFTCHK(st.put(oJ, pj, idB));
+    if (nStale) VFTCHK(st.put(oStale, stale.data(), (size_t) nStale * 8));
+    if (fusedRefresh) {   // which refresh workgroup each end of a pair has to wait for (-1: none)
+        int32_t *wt = st.host<int32_t>(oWait);
+        for (int64_t t = 0; t < n; t++) {
+            wt[2 * t] = set.where(pi[t]);
+            wt[2 * t + 1] = set.where(pj[t]);
         }
-    } else {
-        if (int r = ensure_scratch(c, 2 * idB + 3 * oB + sB + 64)) return r;
-        dBase = (char *) c->scratch;
-        HIPCHK(c, hipMemcpyAsync(dBase, pi, (size_t) n * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dBase + idB, pj, (size_t) n * 8, hipMemcpyHostToDevice, c->stream));
-        if (nStale)
-            HIPCHK(c, hipMemcpyAsync(dBase + 2 * idB + 3 * oB, stale.data(), (size_t) nStale * 8, hipMemcpyHostToDevice, c->stream));
     }
     if (smallTimes) ts1 = std::chrono::steady_clock::now();
-    int64_t *dI = (int64_t *) dBase, *dJ = (int64_t *) (dBase + idB);
-    const int64_t *dStale = (const int64_t *) (dBase + 2 * idB + 3 * oB);
-    const int32_t *dWait = (const int32_t *) (dBase + 2 * idB + 3 * oB + sB);
-    char *o = dBase + 2 * idB;
+    const int64_t *dI = st.dev<const int64_t>(oI), *dJ = st.dev<const int64_t>(oJ), *dStale = st.dev<const int64_t>(oStale);
+    const int32_t *dWait = st.dev<const int32_t>(oWait);
     if (small && n >= 128 && !c->noPairStaging) {
         // One workgroup per pair reading ITS ids from the host-mapped ring is two 8-byte PCIe reads per pair - 4 000 tiny
         // non-posted reads at 2 000 pairs, ~35 ns per pair of a call that otherwise takes ~25 us.  A copy kernel fetches the
         // inputs with 16-byte-per-lane loads first; the pair kernels then read device memory.
-        char *in = (char *) c->pairIn;
-        const size_t nA = 2 * idB / 16, nB = (sB + wB) / 16;
-        launch(k_copy16x2, dim3(cdiv((int64_t) (nA + nB), 256)), dim3(256), 0, c->stream, (uint4 *) in, (const uint4 *) dBase, (int64_t) nA,
-               (uint4 *) (in + 2 * idB), (const uint4 *) (dBase + 2 * idB + 3 * oB), (int64_t) nB);
-        dI = (int64_t *) in;
-        dJ = (int64_t *) (in + idB);
-        dStale = (const int64_t *) (in + 2 * idB);
-        dWait = (const int32_t *) (in + 2 * idB + sB);
+        char *in = (char *) c->pairIn;   // [i | j | stale | wait]
+        st.to_device(in, oI, oDist - oI, oStale, oEnd - oStale);
+        dI = (const int64_t *) in;
+        dJ = (const int64_t *) (in + (oJ - oI));
+        dStale = (const int64_t *) (in + (oDist - oI));
+        dWait = (const int32_t *) (in + (oDist - oI) + (oWait - oStale));
     }
     SweepArgs sa{};
     sa.nActive = nActive;
@@ -2713,16 +2729,16 @@ static int pair_distances(vft_ctx *c, int64_t n, const int64_t *pi, const int64_
     if (fusedRefresh) {   // short list that needs refreshes: one launch, pair workgroups wait on the stamps of flagged ends
         const size_t lds = pw_lds_bytes(c) / c->pwWaves;
         VFT_DISPATCH(c, (launch((k_pairs_refresh_fused<REAL, NC>), dim3((unsigned) (nStale + n)), dim3(pairThreads), lds, c->stream,
-                                arena<REAL>(c), dStale, nStale, nForced, (const int64_t *) dI, (const int64_t *) dJ,
-                                dWait, n, sa, (REAL *) o, (REAL *) (o + oB),
-                                (REAL *) (o + 2 * oB), c->refDone, c->doneCtr, c->dFlag, seq, (REAL *) c->pairStage, (int64_t) VFT_PAIR_STAGE_CAP)));
+                                arena<REAL>(c), dStale, nStale, nForced, dI, dJ,
+                                dWait, n, sa, st.dev<REAL>(oDist), st.dev<REAL>(oWeight),
+                                st.dev<REAL>(oCrit), c->refDone, c->doneCtr, c->dFlag, seq, (REAL *) c->pairStage, (int64_t) VFT_PAIR_STAGE_CAP)));
     } else if (n <= 2048) {   // short list: a workgroup per pair (all of them resident at once)
         const size_t lds = pw_lds_bytes(c) / c->pwWaves;
         if (nStale)
             VFT_DISPATCH(c, (launch((k_refresh_list<REAL, NC, true>), dim3((unsigned) nStale), dim3(VFT_WG), lds, c->stream,
                                     arena<REAL>(c), dStale, nStale, nForced, sa)));
         VFT_DISPATCH(c, (launch((k_pairs_fused<REAL, NC, true>), dim3((unsigned) n), dim3(pairThreads), lds, c->stream,
-                                arena<REAL>(c), dI, dJ, n, sa, (REAL *) o, (REAL *) (o + oB), (REAL *) (o + 2 * oB),
+                                arena<REAL>(c), dI, dJ, n, sa, st.dev<REAL>(oDist), st.dev<REAL>(oWeight), st.dev<REAL>(oCrit),
                                 c->doneCtr, small ? c->dFlag : (unsigned long long *) nullptr, seq, (REAL *) c->pairStage,
                                 (int64_t) VFT_PAIR_STAGE_CAP)));
     } else {
@@ -2730,20 +2746,20 @@ static int pair_distances(vft_ctx *c, int64_t n, const int64_t *pi, const int64_
             VFT_DISPATCH(c, (launch((k_refresh_list<REAL, NC, false>), dim3(cdiv(nStale, c->pwWaves)), dim3(64 * c->pwWaves),
                                     pw_lds_bytes(c), c->stream, arena<REAL>(c), dStale, nStale, nForced, sa)));
         VFT_DISPATCH(c, (launch((k_pairs_fused<REAL, NC, false>), dim3(cdiv(n, c->pwWaves)), dim3(64 * c->pwWaves), pw_lds_bytes(c),
-                                c->stream, arena<REAL>(c), dI, dJ, n, sa, (REAL *) o, (REAL *) (o + oB),
-                                (REAL *) (o + 2 * oB), c->doneCtr, small ? c->dFlag : (unsigned long long *) nullptr, seq,
+                                c->stream, arena<REAL>(c), dI, dJ, n, sa, st.dev<REAL>(oDist), st.dev<REAL>(oWeight),
+                                st.dev<REAL>(oCrit), c->doneCtr, small ? c->dFlag : (unsigned long long *) nullptr, seq,
                                 (REAL *) nullptr, (int64_t) 0)));
     }
     LAUNCHCHK(c);
+    st.get(dist, oDist, resB);
+    st.get(weight, oWeight, resB);
+    st.get(crit, oCrit, resB);
     if (small) {
         // results were written straight into mapped host memory; the kernel's last wave raises the flag
         if (smallTimes) ts2 = std::chrono::steady_clock::now();
-        if (int r = wait_flag(c, seq)) return r;
+        if (int r = st.wait(Stage::WAIT_FLAG, seq)) return r;
         if (smallTimes) ts3 = std::chrono::steady_clock::now();
-        const char *ho = hBase + 2 * idB;
-        if (dist) memcpy(dist, ho, (size_t) n * rs);
-        if (weight) memcpy(weight, ho + oB, (size_t) n * rs);
-        if (crit) memcpy(crit, ho + 2 * oB, (size_t) n * rs);
+        if (int r = st.deliver()) return r;
         if (smallTimes && n >= 1000) {
             const auto ts4 = std::chrono::steady_clock::now();
             tsPrep += std::chrono::duration<double>(ts1 - ts0).count();
@@ -2767,10 +2783,7 @@ static int pair_distances(vft_ctx *c, int64_t n, const int64_t *pi, const int64_
         tKernel += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         t0 = std::chrono::steady_clock::now();
     }
-    if (dist) HIPCHK(c, hipMemcpyAsync(dist, o, (size_t) n * rs, hipMemcpyDeviceToHost, c->stream));
-    if (weight) HIPCHK(c, hipMemcpyAsync(weight, o + oB, (size_t) n * rs, hipMemcpyDeviceToHost, c->stream));
-    if (crit) HIPCHK(c, hipMemcpyAsync(crit, o + 2 * oB, (size_t) n * rs, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (int r = st.deliver()) return r;
     if (stageTimes) {
         tCopy += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         nCalls++;
@@ -2815,43 +2828,22 @@ extern "C" int vft_block_distances(vft_ctx *c, int64_t nA, const int64_t *a, int
         if (b[t] >= c->maxnode) return fail(c, VFT_ERR_INVALID, "vft_block_distances: b[%lld] out of range", (long long) t);
     // the distinct stale nodes among both lists (as in pair_distances)
     std::vector<int64_t> &stale = c->staleIds;
-    stale.clear();
-    if (c->staleMark.size() != (size_t) c->d.maxNodes) c->staleMark.assign((size_t) c->d.maxNodes, 0u);
-    if (++c->staleEpoch == 0u) {
-        std::fill(c->staleMark.begin(), c->staleMark.end(), 0u);
-        c->staleEpoch = 1u;
-    }
-    for (int pass = 0; pass < 2; pass++) {
-        const int64_t *ids = pass ? b : a, cnt = pass ? nB : nA;
-        for (int64_t t = 0; t < cnt; t++) {
-            const int64_t v = ids[t];
-            if (v >= 0 && (int64_t) c->hNOut[v] - nActive > nDiffAllow && c->staleMark[(size_t) v] != c->staleEpoch) {
-                c->staleMark[(size_t) v] = c->staleEpoch;
-                stale.push_back(v);
-            }
-        }
-    }
+    VftStaleSet set(c->hNOut, c->staleMark, c->staleEpoch, (size_t) c->d.maxNodes, nActive, nDiffAllow, stale);
+    set.add(a, nA);
+    set.add(b, nB);
     const int64_t nStale = (int64_t) stale.size();
-    const size_t rs = c->rs, idB = (((size_t) (nA + nB + nStale) * 8) + 255) & ~(size_t) 255;
-    const size_t oB = (((size_t) nA * (size_t) nB * rs) + 255) & ~(size_t) 255;
-    if (int r = ensure_scratch(c, idB + oB + 256)) return r;
-    char *sBase = (char *) c->scratch;
-    int64_t *dA = (int64_t *) sBase, *dB = dA + nA, *dStale = dB + nB;
-    // ids through the mapped ring when they fit (no staging copy), otherwise plain copies
-    if (idB <= VFT_SMALL_BYTES) {
-        char *h, *d;
-        if (int r = io_alloc(c, idB, &h, &d)) return r;
-        memcpy(h, a, (size_t) nA * 8);
-        memcpy(h + (size_t) nA * 8, b, (size_t) nB * 8);
-        if (nStale) memcpy(h + (size_t) (nA + nB) * 8, stale.data(), (size_t) nStale * 8);
-        dA = (int64_t *) d;
-        dB = dA + nA;
-        dStale = dB + nB;
-    } else {
-        HIPCHK(c, hipMemcpyAsync(dA, a, (size_t) nA * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dB, b, (size_t) nB * 8, hipMemcpyHostToDevice, c->stream));
-        if (nStale) HIPCHK(c, hipMemcpyAsync(dStale, stale.data(), (size_t) nStale * 8, hipMemcpyHostToDevice, c->stream));
-    }
+    const size_t rs = c->rs, outB = (size_t) nA * (size_t) nB * rs;
+    // ids through the mapped ring when they fit (no staging copy), otherwise plain copies; the block itself is scratch on either path
+    VftLayout L;
+    const size_t oA = L.add((size_t) nA * 8), oB = L.add((size_t) nB * 8), oStale = L.add((size_t) nStale * 8);
+    const size_t idB = L.total(), oOut = L.add(outB, 256);
+    Stage st, res;
+    if (int r = res.open(c, L.total(), Stage::SCRATCH_ONLY)) return r;
+    if (int r = st.open(c, idB, VFT_SMALL_BYTES)) return r;
+    VFTCHK(st.put(oA, a, (size_t) nA * 8));
+    VFTCHK(st.put(oB, b, (size_t) nB * 8));
+    if (nStale) VFTCHK(st.put(oStale, stale.data(), (size_t) nStale * 8));
+    const int64_t *dA = st.dev<const int64_t>(oA), *dB = st.dev<const int64_t>(oB), *dStale = st.dev<const int64_t>(oStale);
     SweepArgs sa{};
     sa.nActive = nActive;
     sa.nDiffAllow = nDiffAllow;
@@ -2859,13 +2851,11 @@ extern "C" int vft_block_distances(vft_ctx *c, int64_t nA, const int64_t *a, int
     if (nStale) {
         if (nActive > c->maxStamp) c->maxStamp = nActive;
         VFT_DISPATCH(c, (launch((k_refresh_list<REAL, NC, false>), dim3(cdiv(nStale, c->pwWaves)), dim3(64 * c->pwWaves), pw_lds_bytes(c),
-                                c->stream, arena<REAL>(c), (const int64_t *) dStale, nStale, (int64_t) 0, sa)));
+                                c->stream, arena<REAL>(c), dStale, nStale, (int64_t) 0, sa)));
     }
-    char *o = sBase + idB;
-    if (int r = launch_pairs_block(c, (const int64_t *) dA, nA, (const int64_t *) dB, nB, o)) return r;
-    HIPCHK(c, hipMemcpyAsync(dist, o, (size_t) nA * (size_t) nB * rs, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VFT_OK;
+    if (int r = launch_pairs_block(c, dA, nA, dB, nB, res.dev<char>(oOut))) return r;
+    res.get(dist, oOut, outB);
+    return res.finish();
 }
 
 extern "C" int vft_leaf_block_distances(vft_ctx *c, int64_t nA, const int64_t *a, int64_t nB, const int64_t *b, int64_t nActive,
@@ -2878,56 +2868,42 @@ extern "C" int vft_leaf_block_distances(vft_ctx *c, int64_t nA, const int64_t *a
         if (a[t] < 0 || a[t] >= c->d.nSeqs) return fail(c, VFT_ERR_INVALID, "vft_leaf_block_distances: a[%lld] is not a leaf", (long long) t);
     for (int64_t t = 0; t < nB; t++)
         if (b[t] >= c->d.nSeqs) return fail(c, VFT_ERR_INVALID, "vft_leaf_block_distances: b[%lld] is not a leaf", (long long) t);
-    const size_t rs = c->rs, idB = (((size_t) (nA + nB) * 8) + 255) & ~(size_t) 255;
-    const size_t oB = (((size_t) nA * (size_t) nB * rs) + 255) & ~(size_t) 255;
-    if (int r = ensure_scratch(c, idB + 3 * oB + 256)) return r;
-    char *s = (char *) c->scratch;
-    int64_t *dA = (int64_t *) s, *dB = dA + nA;
-    HIPCHK(c, hipMemcpyAsync(dA, a, (size_t) nA * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dB, b, (size_t) nB * 8, hipMemcpyHostToDevice, c->stream));
-    // lazy refresh of whatever is stale (the host-mapped stamp mirror can only lag towards "staler")
-    bool anyStale = false;
-    for (int64_t t = 0; t < nA && !anyStale; t++) anyStale = (int64_t) c->hNOut[a[t]] - nActive > nDiffAllow;
-    for (int64_t t = 0; t < nB && !anyStale; t++) anyStale = b[t] >= 0 && (int64_t) c->hNOut[b[t]] - nActive > nDiffAllow;
-    if (anyStale) {
-        std::vector<int64_t> ids;
-        for (int64_t t = 0; t < nA; t++) ids.push_back(a[t]);
-        for (int64_t t = 0; t < nB; t++)
-            if (b[t] >= 0) ids.push_back(b[t]);
-        std::sort(ids.begin(), ids.end());
-        ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-        int64_t *dIds = (int64_t *) (s + idB + 3 * oB);
-        if (int r = ensure_scratch(c, idB + 3 * oB + 256 + ids.size() * 8)) return r;
-        s = (char *) c->scratch;   // (ensure_scratch may have moved it: re-derive everything)
-        dA = (int64_t *) s;
-        dB = dA + nA;
-        dIds = (int64_t *) (s + idB + 3 * oB);
-        HIPCHK(c, hipMemcpyAsync(dA, a, (size_t) nA * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dB, b, (size_t) nB * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dIds, ids.data(), ids.size() * 8, hipMemcpyHostToDevice, c->stream));
+    // lazy refresh of whatever is stale: the distinct stale leaves in ascending order, sized into the layout before anything is uploaded
+    std::vector<int64_t> &stale = c->staleIds;
+    VftStaleSet set(c->hNOut, c->staleMark, c->staleEpoch, (size_t) c->d.maxNodes, nActive, nDiffAllow, stale);
+    set.add(a, nA);
+    set.add(b, nB);
+    std::sort(stale.begin(), stale.end());
+    const int64_t nStale = (int64_t) stale.size();
+    const size_t rs = c->rs, outB = (size_t) nA * (size_t) nB * rs;
+    VftLayout L;
+    const size_t oA = L.add((size_t) nA * 8), oB = L.add((size_t) nB * 8), oDist = L.add(outB, 256), oWeight = L.add(outB, 256),
+                 oCrit = L.add(outB, 256), oStale = L.add((size_t) nStale * 8, 256);
+    Stage st;
+    if (int r = st.open(c, L.total(), Stage::SCRATCH_ONLY)) return r;
+    VFTCHK(st.put(oA, a, (size_t) nA * 8));
+    VFTCHK(st.put(oB, b, (size_t) nB * 8));
+    if (nStale) {
+        VFTCHK(st.put(oStale, stale.data(), (size_t) nStale * 8));
         if (nActive > c->maxStamp) c->maxStamp = nActive;
-        if (int r = launch_out_distances(c, dIds, (int64_t) ids.size(), nActive, nDiffAllow, totdiam, false)) return r;
-        HIPCHK(c, hipStreamSynchronize(c->stream));   // ids is a local
+        if (int r = launch_out_distances(c, st.dev<const int64_t>(oStale), nStale, nActive, nDiffAllow, totdiam, false)) return r;
     }
     SweepArgs sa{};
     sa.nActive = nActive;
     sa.nDiffAllow = nDiffAllow;
     sa.totdiam = totdiam;
-    char *o = s + idB;
     const dim3 grid(cdiv(nB, 64), cdiv(nA, 64));
     if (c->cfg.precision == 4)
-        launch((k_leaf_block<float>), grid, dim3(VFT_WG), 0, c->stream, arena<float>(c), (const int64_t *) dA, nA, (const int64_t *) dB, nB, sa,
-               (float *) o, (float *) (o + oB), (float *) (o + 2 * oB));
+        launch((k_leaf_block<float>), grid, dim3(VFT_WG), 0, c->stream, arena<float>(c), st.dev<const int64_t>(oA), nA, st.dev<const int64_t>(oB), nB, sa,
+               st.dev<float>(oDist), st.dev<float>(oWeight), st.dev<float>(oCrit));
     else
-        launch((k_leaf_block<double>), grid, dim3(VFT_WG), 0, c->stream, arena<double>(c), (const int64_t *) dA, nA, (const int64_t *) dB, nB, sa,
-               (double *) o, (double *) (o + oB), (double *) (o + 2 * oB));
+        launch((k_leaf_block<double>), grid, dim3(VFT_WG), 0, c->stream, arena<double>(c), st.dev<const int64_t>(oA), nA, st.dev<const int64_t>(oB), nB, sa,
+               st.dev<double>(oDist), st.dev<double>(oWeight), st.dev<double>(oCrit));
     LAUNCHCHK(c);
-    const size_t bytes = (size_t) nA * (size_t) nB * rs;
-    HIPCHK(c, hipMemcpyAsync(dist, o, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(weight, o + oB, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(crit, o + 2 * oB, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VFT_OK;
+    st.get(dist, oDist, outB);
+    st.get(weight, oWeight, outB);
+    st.get(crit, oCrit, outB);
+    return st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------- all-pairs matrix (-makematrix)
@@ -3078,13 +3054,13 @@ extern "C" int vft_exhaustive_search(vft_ctx *c, int64_t nActive, vft_exhaustive
     if (!c->exM || c->exLive < 2) return fail(c, VFT_ERR_STATE, "vft_exhaustive_search before vft_exhaustive_fill");
     if (nActive != c->exLive || nActive < 3)
         return fail(c, VFT_ERR_INVALID, "vft_exhaustive_search: n_active is %lld, the matrix holds %lld nodes", (long long) nActive, (long long) c->exLive);
-    char *h, *d;
-    if (int r = io_alloc(c, sizeof(ExBestOut), &h, &d)) return r;
+    Stage st;
+    if (int r = st.open(c, sizeof(ExBestOut), Stage::RING_ONLY)) return r;
     const unsigned long long seq = ++c->signalSeq;
-    if (int r = c->rs == 4 ? exhaustive_search<float>(c, nActive, (ExBestOut *) d, seq) : exhaustive_search<double>(c, nActive, (ExBestOut *) d, seq))
+    if (int r = c->rs == 4 ? exhaustive_search<float>(c, nActive, st.dev<ExBestOut>(0), seq) : exhaustive_search<double>(c, nActive, st.dev<ExBestOut>(0), seq))
         return r;
-    if (int r = wait_flag(c, seq)) return r;
-    const ExBestOut *o = (const ExBestOut *) h;
+    if (int r = st.wait(Stage::WAIT_FLAG, seq)) return r;
+    const ExBestOut *o = st.host<const ExBestOut>(0);
     if (o->stale)
         return fail(c, VFT_ERR_STATE, "vft_exhaustive_search: out-distances are not current for n_active = %lld (vft_out_distances first)", (long long) nActive);
     out->i = o->i;
@@ -3163,22 +3139,22 @@ extern "C" int vft_tophits_upload(vft_ctx *c, int64_t count, const int64_t *node
     for (int64_t t = 0; t < count; t++)
         if (nodes[t] < 0 || nodes[t] >= c->thLists || lens[t] < 0 || lens[t] > c->thM) return fail(c, VFT_ERR_INVALID, "vft_tophits_upload: list %lld out of range", (long long) t);
     const size_t hitB = c->rs == 4 ? sizeof(ThHit<float>) : sizeof(ThHit<double>);
-    const size_t idB = (((size_t) count * 8) + 255) & ~(size_t) 255, lenB = (((size_t) count * 4) + 255) & ~(size_t) 255;
     const size_t pkB = (size_t) count * (size_t) c->thM * hitB;
-    if (int r = ensure_scratch(c, idB + lenB + pkB + 256)) return r;
-    char *sb = (char *) c->scratch;
-    HIPCHK(c, hipMemcpyAsync(sb, nodes, (size_t) count * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sb + idB, lens, (size_t) count * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sb + idB + lenB, packed, pkB, hipMemcpyHostToDevice, c->stream));
+    VftLayout L;
+    const size_t oNodes = L.add((size_t) count * 8), oLens = L.add((size_t) count * 4, 256), oPacked = L.add(pkB, 256);
+    Stage st;
+    if (int r = st.open(c, L.total(), Stage::SCRATCH_ONLY)) return r;
+    VFTCHK(st.put(oNodes, nodes, (size_t) count * 8));
+    VFTCHK(st.put(oLens, lens, (size_t) count * 4));
+    VFTCHK(st.put(oPacked, packed, pkB));
     if (c->rs == 4)
-        launch((k_th_scatter<float>), dim3((unsigned) count), dim3(256), 0, c->stream, tophits<float>(c), (const int64_t *) sb,
-               (const int32_t *) (sb + idB), (const ThHit<float> *) (sb + idB + lenB));
+        launch((k_th_scatter<float>), dim3((unsigned) count), dim3(256), 0, c->stream, tophits<float>(c), st.dev<const int64_t>(oNodes),
+               st.dev<const int32_t>(oLens), st.dev<const ThHit<float>>(oPacked));
     else
-        launch((k_th_scatter<double>), dim3((unsigned) count), dim3(256), 0, c->stream, tophits<double>(c), (const int64_t *) sb,
-               (const int32_t *) (sb + idB), (const ThHit<double> *) (sb + idB + lenB));
+        launch((k_th_scatter<double>), dim3((unsigned) count), dim3(256), 0, c->stream, tophits<double>(c), st.dev<const int64_t>(oNodes),
+               st.dev<const int32_t>(oLens), st.dev<const ThHit<double>>(oPacked));
     LAUNCHCHK(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // the caller's buffers are pageable: the copies may still be reading them
-    return VFT_OK;
+    return st.finish();   // the caller's buffers are pageable: the copies may still be reading them
 }
 
 extern "C" int vft_tophits_download(vft_ctx *c, int64_t node, int32_t *len, void *hits) {
@@ -3219,14 +3195,14 @@ extern "C" int vft_tophits_best(vft_ctx *c, int64_t node, int32_t len, int64_t n
     sa.totdiam = totdiam;
     tophits_refresh_own(c, node, sa, forceNode != 0);
     if (nActive > c->maxStamp) c->maxStamp = nActive;   // the walk may refresh partners
-    char *h, *d;
-    if (int r = io_alloc(c, sizeof(ThBestOut), &h, &d)) return r;
+    Stage st;
+    if (int r = st.open(c, sizeof(ThBestOut), Stage::RING_ONLY)) return r;
     const unsigned long long seq = ++c->signalSeq;
     VFT_DISPATCH(c, (launch((k_th_best<REAL, NC>), dim3((unsigned) len), dim3(VFT_WG), c->thLds, c->stream, arena<REAL>(c),
-                            tophits<REAL>(c), node, sa, (ThBestOut *) d, c->dFlag, seq)));
+                            tophits<REAL>(c), node, sa, st.dev<ThBestOut>(0), c->dFlag, seq)));
     LAUNCHCHK(c);
-    if (int r = wait_flag(c, seq)) return r;
-    const ThBestOut *o = (const ThBestOut *) h;
+    if (int r = st.wait(Stage::WAIT_FLAG, seq)) return r;
+    const ThBestOut *o = st.host<const ThBestOut>(0);
     out->j = o->j;
     out->pos = o->pos;
     out->dist = o->dist;
@@ -3253,28 +3229,30 @@ extern "C" int vft_tophits_join(vft_ctx *c, int64_t newnode, int64_t c0, int32_t
     sa.totdiam = totdiam;
     tophits_refresh_own(c, newnode, sa, false);   // the new node's stamp is "unreasonably high" (NJ.tcc:254): the lazy rule fires
     if (nActive > c->maxStamp) c->maxStamp = nActive;
-    const size_t rs = c->rs, aB = (((size_t) n * 8) + 255) & ~(size_t) 255;
-    char *h, *d;
-    if (int r = io_alloc(c, 256 + 3 * aB, &h, &d)) return r;
+    const size_t rs = c->rs;
+    VftLayout L;   // (three arrays of 8 bytes per candidate, whatever they hold)
+    const size_t oInfo = L.add(sizeof(ThJoinInfo)), oJ = L.add((size_t) n * 8, 256), oDist = L.add((size_t) n * 8, 256), oCrit = L.add((size_t) n * 8, 256);
+    Stage st;
+    if (int r = st.open(c, L.total(), Stage::RING_ONLY)) return r;
     const unsigned long long seq = ++c->signalSeq;
     if (++c->thTag == 0u) {   // (2^32 joins on one context: start the marks over)
         HIPCHK(c, hipMemsetAsync(c->thMark, 0, (size_t) c->d.maxNodes * 4, c->stream));
         c->thTag = 1u;
     }
     VFT_DISPATCH(c, (launch((k_th_join<REAL, NC>), dim3((unsigned) n), dim3(VFT_WG), c->thLds, c->stream, arena<REAL>(c),
-                            tophits<REAL>(c), newnode, c0, n0, c1, sa, c->thTag, nSaveMax, need, ageOK, (ThJoinInfo *) d,
-                            (int32_t *) (d + 256), (REAL *) (d + 256 + aB), (REAL *) (d + 256 + 2 * aB), c->dFlag, seq)));
+                            tophits<REAL>(c), newnode, c0, n0, c1, sa, c->thTag, nSaveMax, need, ageOK, st.dev<ThJoinInfo>(oInfo),
+                            st.dev<int32_t>(oJ), st.dev<REAL>(oDist), st.dev<REAL>(oCrit), c->dFlag, seq)));
     LAUNCHCHK(c);
-    if (int r = wait_flag(c, seq)) return r;
-    const ThJoinInfo *o = (const ThJoinInfo *) h;
+    if (int r = st.wait(Stage::WAIT_FLAG, seq)) return r;
+    const ThJoinInfo *o = st.host<const ThJoinInfo>(oInfo);
     info->n_unique = o->nUnique;
     info->use_unique = o->useUnique;
     info->n_save = o->nSave;
     info->pad = 0;
-    memcpy(j, h + 256, (size_t) o->nUnique * 4);
-    memcpy(dist, h + 256 + aB, (size_t) o->nUnique * rs);
-    memcpy(crit, h + 256 + 2 * aB, (size_t) o->nUnique * rs);
-    return VFT_OK;
+    st.get(j, oJ, (size_t) o->nUnique * 4);   // (how many: known only now)
+    st.get(dist, oDist, (size_t) o->nUnique * rs);
+    st.get(crit, oCrit, (size_t) o->nUnique * rs);
+    return st.deliver();
 }
 
 extern "C" int vft_tophits_refresh(vft_ctx *c, int64_t newnode, int32_t nHits, const int64_t *hitJ, const void *hitDist, int32_t nOwn,
@@ -3299,23 +3277,24 @@ extern "C" int vft_tophits_refresh(vft_ctx *c, int64_t newnode, int32_t nHits, c
     while (P < E) P <<= 1;
     const size_t lds = pw_lds_bytes(c) / c->pwWaves + (size_t) P * sizeof(ThKey) + (size_t) E * 16 + (size_t) E * rs;
     if (lds > (160u << 10) - 1024) return fail(c, VFT_ERR_STATE, "vft_tophits_refresh: %zu bytes of LDS per node", lds);
-    // input block: targets | distances | work | nNew | own list   (host-mapped ring, then one copy to device memory)
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t) 255; };
-    const size_t oT = 0, oD = oT + pad((size_t) nB * 8), oW = oD + pad((size_t) nB * rs), oN = oW + pad((size_t) nWork * 8),
-                 oO = oN + pad((size_t) nWork * 4), inB = oO + pad((size_t) nOwn * hitB);
-    const size_t oLen = 0, oFirst = pad((size_t) nWork * 4), outB = oFirst + pad((size_t) nWork * hitB);
-    char *h, *d;
-    if (int r = io_alloc(c, inB + outB, &h, &d)) return r;
-    memcpy(h + oT, hitJ, (size_t) nB * 8);
-    memcpy(h + oD, hitDist, (size_t) nB * rs);
-    if (nWork) memcpy(h + oW, work, (size_t) nWork * 8);
-    if (nWork) memcpy(h + oN, nNew, (size_t) nWork * 4);
-    if (nOwn) memcpy(h + oO, ownList, (size_t) nOwn * hitB);
-    const size_t blockB = pad((size_t) nWork * (size_t) nB * rs);
-    if (int r = ensure_scratch(c, inB + blockB + 256)) return r;
-    char *sIn = (char *) c->scratch, *sBlock = sIn + inB;
-    launch(k_copy16x2, dim3(cdiv((int64_t) (inB / 16), 256)), dim3(256), 0, c->stream, (uint4 *) sIn, (const uint4 *) d, (int64_t) (inB / 16),
-           (uint4 *) nullptr, (const uint4 *) nullptr, (int64_t) 0);
+    // input block: targets | distances | work | nNew | own list, then the results (host-mapped ring); the inputs go on to device memory
+    // in one copy, in front of the block of distances (scratch)
+    VftLayout L, W;
+    const size_t oT = L.add((size_t) nB * 8, 256), oD = L.add((size_t) nB * rs, 256), oW = L.add((size_t) nWork * 8, 256),
+                 oN = L.add((size_t) nWork * 4, 256), oO = L.add((size_t) nOwn * hitB, 256), inB = L.add(0, 256);
+    const size_t oLen = L.add((size_t) nWork * 4, 256), oFirst = L.add((size_t) nWork * hitB, 256);
+    W.add(inB);
+    const size_t oBlock = W.add((size_t) nWork * (size_t) nB * rs, 256);
+    Stage st, blk;
+    if (int r = st.open(c, L.total(), Stage::RING_ONLY)) return r;
+    st.put(oT, hitJ, (size_t) nB * 8);
+    st.put(oD, hitDist, (size_t) nB * rs);
+    if (nWork) st.put(oW, work, (size_t) nWork * 8);
+    if (nWork) st.put(oN, nNew, (size_t) nWork * 4);
+    if (nOwn) st.put(oO, ownList, (size_t) nOwn * hitB);
+    if (int r = blk.open(c, W.total(), Stage::SCRATCH_ONLY)) return r;
+    char *sIn = blk.dev<char>(0), *sBlock = blk.dev<char>(oBlock);
+    st.to_device(sIn, oT, inB);
     SweepArgs sa{};
     sa.nActive = nActive;
     sa.nDiffAllow = nDiffAllow;
@@ -3327,33 +3306,18 @@ extern "C" int vft_tophits_refresh(vft_ctx *c, int64_t newnode, int32_t nHits, c
         return VFT_OK;   // (stream-ordered: the next walk sees the list)
     }
     // setCriterion's lazy refresh for every node the block names (none after NJ.tcc:4451-4464; kept for callers that skip it)
-    {
-        std::vector<int64_t> &stale = c->staleIds;
-        stale.clear();
-        if (c->staleMark.size() != (size_t) c->d.maxNodes) c->staleMark.assign((size_t) c->d.maxNodes, 0u);
-        if (++c->staleEpoch == 0u) {
-            std::fill(c->staleMark.begin(), c->staleMark.end(), 0u);
-            c->staleEpoch = 1u;
-        }
-        for (int pass = 0; pass < 2; pass++) {
-            const int64_t *ids = pass ? hitJ : work, cnt = pass ? nB : nWork;
-            for (int64_t t = 0; t < cnt; t++) {
-                const int64_t v = ids[t];
-                if (v >= 0 && (int64_t) c->hNOut[v] - nActive > nDiffAllow && c->staleMark[(size_t) v] != c->staleEpoch) {
-                    c->staleMark[(size_t) v] = c->staleEpoch;
-                    stale.push_back(v);
-                }
-            }
-        }
-        if (!stale.empty()) {
-            const int64_t nStale = (int64_t) stale.size();
-            char *hs, *ds;
-            if (int r = io_alloc(c, (size_t) nStale * 8, &hs, &ds)) return r;
-            memcpy(hs, stale.data(), (size_t) nStale * 8);
-            if (nActive > c->maxStamp) c->maxStamp = nActive;
-            VFT_DISPATCH(c, (launch((k_refresh_list<REAL, NC, false>), dim3(cdiv(nStale, c->pwWaves)), dim3(64 * c->pwWaves), pw_lds_bytes(c),
-                                    c->stream, arena<REAL>(c), (const int64_t *) ds, nStale, (int64_t) 0, sa)));
-        }
+    std::vector<int64_t> &stale = c->staleIds;
+    VftStaleSet set(c->hNOut, c->staleMark, c->staleEpoch, (size_t) c->d.maxNodes, nActive, nDiffAllow, stale);
+    set.add(work, nWork);
+    set.add(hitJ, nB);
+    if (!stale.empty()) {
+        const int64_t nStale = (int64_t) stale.size();
+        Stage ids;
+        if (int r = ids.open(c, (size_t) nStale * 8, Stage::RING_ONLY)) return r;
+        ids.put(0, stale.data(), (size_t) nStale * 8);
+        if (nActive > c->maxStamp) c->maxStamp = nActive;
+        VFT_DISPATCH(c, (launch((k_refresh_list<REAL, NC, false>), dim3(cdiv(nStale, c->pwWaves)), dim3(64 * c->pwWaves), pw_lds_bytes(c),
+                                c->stream, arena<REAL>(c), ids.dev<const int64_t>(0), nStale, (int64_t) 0, sa)));
     }
     if (int r = launch_pairs_block(c, (const int64_t *) (sIn + oW), nWork, (const int64_t *) (sIn + oT), (int64_t) nB, sBlock)) return r;
     if (lds > c->thRefreshLds) {
@@ -3361,16 +3325,14 @@ extern "C" int vft_tophits_refresh(vft_ctx *c, int64_t newnode, int32_t nHits, c
         c->thRefreshLds = lds;
     }
     const unsigned long long seq = ++c->signalSeq;
-    char *dOut = d + inB;
     VFT_DISPATCH(c, (launch((k_th_refresh<REAL, NC>), dim3((unsigned) nWork), dim3(VFT_WG), lds, c->stream, arena<REAL>(c), tophits<REAL>(c),
                             newnode, (const int64_t *) (sIn + oW), (const int32_t *) (sIn + oN), (const int64_t *) (sIn + oT),
-                            (const REAL *) (sIn + oD), nB, (const REAL *) sBlock, sa, P, E, (int32_t *) (dOut + oLen),
-                            (ThHit<REAL> *) (dOut + oFirst), c->dFlag, seq)));
+                            (const REAL *) (sIn + oD), nB, (const REAL *) sBlock, sa, P, E, st.dev<int32_t>(oLen),
+                            st.dev<ThHit<REAL>>(oFirst), c->dFlag, seq)));
     LAUNCHCHK(c);
-    if (int r = wait_flag(c, seq)) return r;
-    memcpy(lens, h + inB + oLen, (size_t) nWork * 4);
-    memcpy(first, h + inB + oFirst, (size_t) nWork * hitB);
-    return VFT_OK;
+    st.get(lens, oLen, (size_t) nWork * 4);
+    st.get(first, oFirst, (size_t) nWork * hitB);
+    return st.finish(Stage::WAIT_FLAG, seq);
 }
 
 // ---------------------------------------------------------------------------------------------- join engine
@@ -3559,40 +3521,31 @@ extern "C" int vft_nj_engine_nodes_set(vft_ctx *c, int64_t n, const int64_t *nod
     if (n == 0) return VFT_OK;
     for (int64_t t = 0; t < n; t++)
         if (nodes[t] < 0 || nodes[t] >= c->d.maxNodes) return fail(c, VFT_ERR_INVALID, "vft_nj_engine_nodes_set: node %lld out of range", (long long) t);
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t) 255; };
-    const size_t oN = 0, oJ = pad((size_t) n * 8), oD = oJ + pad((size_t) n * 4), tot = oD + pad((size_t) n * c->rs);
-    char *h, *d;
-    if (tot <= VFT_SMALL_BYTES) {
-        if (int r = io_alloc(c, tot, &h, &d)) return r;
-        memcpy(h + oN, nodes, (size_t) n * 8);
-        if (j) memcpy(h + oJ, j, (size_t) n * 4);
-        if (j) memcpy(h + oD, dist, (size_t) n * c->rs);
-    } else {
-        if (int r = ensure_scratch(c, tot + 256)) return r;
-        d = (char *) c->scratch;
-        HIPCHK(c, hipMemcpyAsync(d + oN, nodes, (size_t) n * 8, hipMemcpyHostToDevice, c->stream));
-        if (j) HIPCHK(c, hipMemcpyAsync(d + oJ, j, (size_t) n * 4, hipMemcpyHostToDevice, c->stream));
-        if (j) HIPCHK(c, hipMemcpyAsync(d + oD, dist, (size_t) n * c->rs, hipMemcpyHostToDevice, c->stream));
-    }
+    VftLayout L;
+    const size_t oN = L.add((size_t) n * 8, 256), oJ = L.add((size_t) n * 4, 256), oD = L.add((size_t) n * c->rs, 256);
+    Stage st;
+    if (int r = st.open(c, L.add(0, 256), VFT_SMALL_BYTES)) return r;
+    VFTCHK(st.put(oN, nodes, (size_t) n * 8));
+    if (j) VFTCHK(st.put(oJ, j, (size_t) n * 4));
+    if (j) VFTCHK(st.put(oD, dist, (size_t) n * c->rs));
     if (c->rs == 4)
-        launch((k_nj_nodes_set<float>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, njengine<float>(c), (const int64_t *) (d + oN),
-               j ? (const int32_t *) (d + oJ) : (const int32_t *) nullptr, (const float *) (d + oD), n, age);
+        launch((k_nj_nodes_set<float>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, njengine<float>(c), st.dev<const int64_t>(oN),
+               j ? st.dev<const int32_t>(oJ) : nullptr, st.dev<const float>(oD), n, age);
     else
-        launch((k_nj_nodes_set<double>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, njengine<double>(c), (const int64_t *) (d + oN),
-               j ? (const int32_t *) (d + oJ) : (const int32_t *) nullptr, (const double *) (d + oD), n, age);
+        launch((k_nj_nodes_set<double>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, njengine<double>(c), st.dev<const int64_t>(oN),
+               j ? st.dev<const int32_t>(oJ) : nullptr, st.dev<const double>(oD), n, age);
     LAUNCHCHK(c);
-    if (tot > VFT_SMALL_BYTES) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VFT_OK;
+    return st.finish();
 }
 
 extern "C" int vft_nj_engine_topvisible_set(vft_ctx *c, const int32_t *nodes) {
     NJ_ENGINE_OK(c);
     if (!nodes) return VFT_ERR_INVALID;
     const size_t bytes = (size_t) c->njCfg.n_top * 4;
-    char *h, *d;
-    if (int r = io_alloc(c, bytes, &h, &d)) return r;
-    memcpy(h, nodes, bytes);
-    launch(k_copy_i32, dim3(cdiv(c->njCfg.n_top, 256)), dim3(256), 0, c->stream, c->njTop, (const int32_t *) d, (int64_t) c->njCfg.n_top);
+    Stage st;
+    if (int r = st.open(c, bytes, Stage::RING_ONLY)) return r;
+    st.put(0, nodes, bytes);
+    launch(k_copy_i32, dim3(cdiv(c->njCfg.n_top, 256)), dim3(256), 0, c->stream, c->njTop, st.dev<const int32_t>(0), (int64_t) c->njCfg.n_top);
     LAUNCHCHK(c);
     return VFT_OK;
 }
@@ -3609,11 +3562,14 @@ extern "C" int vft_nj_engine_reset_candidates(vft_ctx *c, int64_t nActive, doubl
     NJ_ENGINE_OK(c);
     if (!hits || !nVisible || k < 1 || k > c->hitsCap || nActive < 1) return VFT_ERR_INVALID;
     const int64_t maxnode = c->maxnode;
-    if (int r = ensure_scratch(c, (size_t) maxnode * 8 + 512)) return r;
-    unsigned int *dCnt = (unsigned int *) c->scratch;            // [0] stale nodes, [1] nodes with a usable visible hit
-    int64_t *dList = (int64_t *) ((char *) c->scratch + 256);
-    char *h, *d;
-    if (int r = io_alloc(c, 256, &h, &d)) return r;
+    VftLayout W;
+    const size_t oCnt = W.add(8), oList = W.add((size_t) maxnode * 8, 256);
+    Stage work, pub;   // the work arrays (scratch) and the two counts as the host sees them (ring)
+    if (int r = work.open(c, W.total(), Stage::SCRATCH_ONLY)) return r;
+    unsigned int *dCnt = work.dev<unsigned int>(oCnt);            // [0] stale nodes, [1] nodes with a usable visible hit
+    int64_t *dList = work.dev<int64_t>(oList);
+    if (int r = pub.open(c, 8, Stage::RING_ONLY)) return r;
+    volatile unsigned int *hCnt = pub.host<volatile unsigned int>(0);
     SweepArgs sa{};
     sa.nActive = nActive;
     sa.nDiffAllow = (int64_t) ((double) nActive * c->njCfg.stale_out_limit);
@@ -3627,10 +3583,10 @@ extern "C" int vft_nj_engine_reset_candidates(vft_ctx *c, int64_t nActive, doubl
     // 1. the lazy refreshes (setCriterion inside getVisible, NJ.tcc:1092-1098) of exactly the nodes the reference touches
     if (c->rs == 4) launch((k_nj_reset_stale<float>), dim3(grid), dim3(VFT_WG), 0, c->stream, arena<float>(c), njengine<float>(c), sa, maxnode, c->thMark, c->thTag, dList, dCnt);
     else launch((k_nj_reset_stale<double>), dim3(grid), dim3(VFT_WG), 0, c->stream, arena<double>(c), njengine<double>(c), sa, maxnode, c->thMark, c->thTag, dList, dCnt);
-    launch(k_nj_publish_u32, dim3(1), dim3(64), 0, c->stream, (const unsigned int *) dCnt, (unsigned int *) d, 1);
+    launch(k_nj_publish_u32, dim3(1), dim3(64), 0, c->stream, (const unsigned int *) dCnt, pub.dev<unsigned int>(0), 1);
     LAUNCHCHK(c);
     if (int r = wait_stream(c)) return r;
-    const int64_t nStale = (int64_t) *(volatile unsigned int *) h;
+    const int64_t nStale = (int64_t) hCnt[0];
     if (nStale > 0) {
         if (nActive > c->maxStamp) c->maxStamp = nActive;
         VFT_DISPATCH(c, (launch((k_refresh_list<REAL, NC, false>), dim3(cdiv(nStale, c->pwWaves)), dim3(64 * c->pwWaves), pw_lds_bytes(c), c->stream,
@@ -3641,14 +3597,14 @@ extern "C" int vft_nj_engine_reset_candidates(vft_ctx *c, int64_t nActive, doubl
     c->slots[0].nPart = (int) grid;
     if (c->rs == 4) launch((k_nj_reset_crit<float>), dim3(grid), dim3(VFT_WG), 0, c->stream, arena<float>(c), njengine<float>(c), sa, maxnode, sweepout<float>(c, 0), dCnt + 1);
     else launch((k_nj_reset_crit<double>), dim3(grid), dim3(VFT_WG), 0, c->stream, arena<double>(c), njengine<double>(c), sa, maxnode, sweepout<double>(c, 0), dCnt + 1);
-    launch(k_nj_publish_u32, dim3(1), dim3(64), 0, c->stream, (const unsigned int *) dCnt, (unsigned int *) d, 2);
+    launch(k_nj_publish_u32, dim3(1), dim3(64), 0, c->stream, (const unsigned int *) dCnt, pub.dev<unsigned int>(0), 2);
     LAUNCHCHK(c);
     const int64_t query = -1;
     int r;
     if (c->cfg.precision == 4) r = run_select<float, vft_hit_f32>(c, 1, &query, 0, maxnode, k);
     else r = run_select<double, vft_hit_f64>(c, 1, &query, 0, maxnode, k);
     if (r) return r;
-    *nVisible = (int64_t) ((volatile unsigned int *) h)[1];
+    *nVisible = (int64_t) hCnt[1];
     memcpy(hits, c->slots[0].hRes + sizeof(SelectHeader), (size_t) k * (c->cfg.precision == 4 ? sizeof(vft_hit_f32) : sizeof(vft_hit_f64)));
     return VFT_OK;
 }
@@ -3828,34 +3784,22 @@ extern "C" int vft_pair_loglk(vft_ctx *c, int64_t n, const int64_t *a, const int
     for (int64_t k = 0; k < n; k++)
         if (a[k] < 0 || a[k] >= c->d.maxNodes || b[k] < 0 || b[k] >= c->d.maxNodes) return fail(c, VFT_ERR_INVALID, "vft_pair_loglk: pair %lld out of range", (long long) k);
     const size_t idB = (size_t) n * 8, sB = siteLk ? (size_t) n * c->d.nPos * 8 : 0;
-    if (4 * idB <= 2 * VFT_SMALL_BYTES && !siteLk) {
-        // a batch of a few thousand pairs (treeLogLk of a 10 000-taxon tree, the per-operator tables): ids and lengths travel through
-        // the host-mapped ring and the totals come back through it - three staged copies, a DMA read-back and a stream
-        // synchronisation were 80 of the call's 130 us at 8 192 pairs
-        char *h, *d;
-        if (int r = io_alloc(c, 4 * idB, &h, &d)) return r;
-        memcpy(h, a, idB);
-        memcpy(h + idB, b, idB);
-        memcpy(h + 2 * idB, length, idB);
-        launch_pair_loglk_any(c, n, (const int64_t *) d, (const int64_t *) (d + idB), (const double *) (d + 2 * idB), (double *) (d + 3 * idB), (double *) nullptr);
-        LAUNCHCHK(c);
-        if (int r = wait_stream(c)) return r;
-        memcpy(loglk, h + 3 * idB, idB);
-        return VFT_OK;
-    }
-    if (int r = ensure_scratch(c, 4 * idB + sB + 64)) return r;
-    char *s = (char *) c->scratch;
-    HIPCHK(c, hipMemcpyAsync(s, a, idB, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(s + idB, b, idB, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(s + 2 * idB, length, idB, hipMemcpyHostToDevice, c->stream));
-    double *dOut = (double *) (s + 3 * idB);
-    double *dSite = siteLk ? (double *) (s + 4 * idB) : nullptr;
-    launch_pair_loglk_any(c, n, (const int64_t *) s, (const int64_t *) (s + idB), (const double *) (s + 2 * idB), dOut, dSite);
+    // a batch of a few thousand pairs (treeLogLk of a 10 000-taxon tree, the per-operator tables): ids and lengths travel through
+    // the host-mapped ring and the totals come back through it - three staged copies, a DMA read-back and a stream
+    // synchronisation were 80 of the call's 130 us at 8 192 pairs.  Per-site likelihoods always take the scratch.
+    VftLayout L;
+    const size_t oA = L.add(idB), oB = L.add(idB), oLen = L.add(idB), oOut = L.add(idB), oSite = L.add(sB);
+    Stage st;
+    if (int r = st.open(c, L.total(), siteLk ? Stage::SCRATCH_ONLY : 2 * VFT_SMALL_BYTES)) return r;
+    VFTCHK(st.put(oA, a, idB));
+    VFTCHK(st.put(oB, b, idB));
+    VFTCHK(st.put(oLen, length, idB));
+    launch_pair_loglk_any(c, n, st.dev<const int64_t>(oA), st.dev<const int64_t>(oB), st.dev<const double>(oLen), st.dev<double>(oOut),
+                          siteLk ? st.dev<double>(oSite) : nullptr);
     LAUNCHCHK(c);
-    HIPCHK(c, hipMemcpyAsync(loglk, dOut, idB, hipMemcpyDeviceToHost, c->stream));
-    if (siteLk) HIPCHK(c, hipMemcpyAsync(siteLk, dSite, sB, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VFT_OK;
+    st.get(loglk, oOut, idB);
+    st.get(siteLk, oSite, sB);
+    return st.finish(Stage::WAIT_STREAM);
 }
 
 extern "C" int vft_posterior_profiles(vft_ctx *c, int64_t n, const int64_t *out, const int64_t *a, const int64_t *b,
@@ -3870,52 +3814,42 @@ extern "C" int vft_posterior_profiles(vft_ctx *c, int64_t n, const int64_t *out,
     const CommitPlan plan = commit_plan(c, n);
     const int64_t chunk = plan.chunk;
     const size_t idB = (size_t) n * 8;
-    if (int r = ensure_scratch(c, 5 * idB + plan.totalB + 512)) return r;
-    char *s = (char *) c->scratch;
-    char *base = s + 5 * idB;
-    base += (256 - ((uintptr_t) base & 255)) & 255;
-    const bool viaRing = 5 * idB <= 2 * VFT_SMALL_BYTES;   // (five staged copies cost more than the kernel at a few thousand nodes)
-    if (viaRing) {
-        char *h, *d;
-        if (int r = io_alloc(c, 5 * idB, &h, &d)) return r;
-        memcpy(h, out, idB);
-        memcpy(h + idB, a, idB);
-        memcpy(h + 2 * idB, b, idB);
-        memcpy(h + 3 * idB, len1, idB);
-        memcpy(h + 4 * idB, len2, idB);
-        launch(k_copy16x2, dim3(cdiv((int64_t) (5 * idB + 15) / 16, 256)), dim3(256), 0, c->stream, (uint4 *) s, (const uint4 *) d, (int64_t) (5 * idB + 15) / 16,
-               (uint4 *) nullptr, (const uint4 *) nullptr, (int64_t) 0);
-    } else {
-    HIPCHK(c, hipMemcpyAsync(s, out, idB, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(s + idB, a, idB, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(s + 2 * idB, b, idB, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(s + 3 * idB, len1, idB, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(s + 4 * idB, len2, idB, hipMemcpyHostToDevice, c->stream));
-    }
+    // The kernels read the five lists from the scratch on either path: short ones travel through the ring and one copy kernel (five
+    // staged copies cost more than the kernel at a few thousand nodes).  Behind them, the commit plan's block.
+    VftLayout L;
+    const size_t oOut = L.add(idB), oA = L.add(idB), oB = L.add(idB), oLen1 = L.add(idB), oLen2 = L.add(idB), listsB = L.total();
+    const size_t oBase = L.add(plan.totalB, 256);
+    Stage st, in;
+    if (int r = st.open(c, L.total(), Stage::SCRATCH_ONLY)) return r;
+    if (int r = in.open(c, listsB, 2 * VFT_SMALL_BYTES)) return r;
+    VFTCHK(in.put(oOut, out, idB));
+    VFTCHK(in.put(oA, a, idB));
+    VFTCHK(in.put(oB, b, idB));
+    VFTCHK(in.put(oLen1, len1, idB));
+    VFTCHK(in.put(oLen2, len2, idB));
+    if (in.ring) in.to_device(st.d, oOut, listsB);
+    const int64_t *dOut = st.dev<const int64_t>(oOut), *dA = st.dev<const int64_t>(oA), *dB = st.dev<const int64_t>(oB);
+    const double *dLen1 = st.dev<const double>(oLen1), *dLen2 = st.dev<const double>(oLen2);
+    char *base = st.dev<char>(oBase);
     // Row mode with every internal profile a row (the ML stage, vft_set_profile_rows): the results go to the nodes' dense rows - what every
     // reader takes from then on - with no stash and no tile commit, as vft_posterior_profiles_blen writes them
     const bool rows = c->rowMode && c->allRows && c->mlIs != nullptr;
     for (int64_t k0 = 0; k0 < n; k0 += chunk) {
         const int64_t cnt = n - k0 < chunk ? n - k0 : chunk;
         if (rows) {
-            launch_posterior_rows(c, cnt, (const int64_t *) s + k0, (const int64_t *) (s + idB) + k0, (const int64_t *) (s + 2 * idB) + k0,
-                                  (const double *) (s + 3 * idB) + k0, (const double *) (s + 4 * idB) + k0);
+            launch_posterior_rows(c, cnt, dOut + k0, dA + k0, dB + k0, dLen1 + k0, dLen2 + k0);
             LAUNCHCHK(c);
             continue;
         }
         VFT_DISPATCH(c, {
             const dim3 grid(cdiv(c->d.nPos, VFT_ML_WG), (unsigned) cnt);
-            launch((k_posterior<REAL, NC>), grid, dim3(VFT_ML_WG), 0, c->stream, arena<REAL>(c), (const int64_t *) s + k0,
-                   (const int64_t *) (s + idB) + k0, (const int64_t *) (s + 2 * idB) + k0,
-                   (const double *) (s + 3 * idB) + k0, (const double *) (s + 4 * idB) + k0, c->minLen, c->minRel,
-                   (REAL *) base);
+            launch((k_posterior<REAL, NC>), grid, dim3(VFT_ML_WG), 0, c->stream, arena<REAL>(c), dOut + k0, dA + k0, dB + k0, dLen1 + k0,
+                   dLen2 + k0, c->minLen, c->minRel, (REAL *) base);
         });
         LAUNCHCHK(c);
-        if (int r = commit_nodes(c, plan, out + k0, (const int64_t *) s + k0, cnt, base)) return r;
+        if (int r = commit_nodes(c, plan, out + k0, dOut + k0, cnt, base)) return r;
     }
-    if (viaRing) return wait_stream(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VFT_OK;
+    return in.finish(Stage::WAIT_STREAM);
 }
 
 // ---------------------------------------------------------------------------------------------- ML branch lengths
@@ -3961,23 +3895,25 @@ static int blen_indexed(vft_ctx *c, int64_t n, const int64_t *idx, void *values,
     for (int64_t k = 0; k < n; k++)
         if (idx[k] < 0 || idx[k] >= c->d.maxNodes) return fail(c, VFT_ERR_INVALID, "vft_branch_lengths_%s: index out of range", gather ? "gather" : "scatter");
     if (int r = ensure_blen(c)) return r;
-    const size_t ib = ((size_t) n * 8 + 255) & ~(size_t) 255, vb = ((size_t) n * c->rs + 255) & ~(size_t) 255;
-    char *h, *d;
-    if (int r = io_alloc(c, ib + vb, &h, &d)) return r;
-    memcpy(h, idx, (size_t) n * 8);
-    if (!gather) memcpy(h + ib, values, (size_t) n * c->rs);
+    const size_t vb = (size_t) n * c->rs;
+    VftLayout L;
+    const size_t oIdx = L.add((size_t) n * 8), oVal = L.add(vb, 256);
+    Stage st;
+    if (int r = st.open(c, L.total(), Stage::RING_ONLY)) return r;
+    st.put(oIdx, idx, (size_t) n * 8);
+    if (!gather) st.put(oVal, values, vb);
+    const int64_t *dIdx = st.dev<const int64_t>(oIdx);
     if (c->cfg.precision == 4) {
-        if (gather) launch((k_blen_gather<float>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const float *) c->blen, (const int64_t *) d, (float *) (d + ib), n);
-        else launch((k_blen_scatter<float>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (float *) c->blen, (const int64_t *) d, (const float *) (d + ib), n);
+        if (gather) launch((k_blen_gather<float>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const float *) c->blen, dIdx, st.dev<float>(oVal), n);
+        else launch((k_blen_scatter<float>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (float *) c->blen, dIdx, st.dev<const float>(oVal), n);
     } else {
-        if (gather) launch((k_blen_gather<double>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double *) c->blen, (const int64_t *) d, (double *) (d + ib), n);
-        else launch((k_blen_scatter<double>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (double *) c->blen, (const int64_t *) d, (const double *) (d + ib), n);
+        if (gather) launch((k_blen_gather<double>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double *) c->blen, dIdx, st.dev<double>(oVal), n);
+        else launch((k_blen_scatter<double>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (double *) c->blen, dIdx, st.dev<const double>(oVal), n);
     }
     LAUNCHCHK(c);
     if (!gather) return VFT_OK;   // stream-ordered: the kernels that read the lengths queue behind it
-    if (int r = wait_stream(c)) return r;
-    memcpy(values, h + ib, (size_t) n * c->rs);
-    return VFT_OK;
+    st.get(values, oVal, vb);
+    return st.finish(Stage::WAIT_STREAM);
 }
 extern "C" int vft_branch_lengths_gather(vft_ctx *c, int64_t n, const int64_t *idx, void *values) { return blen_indexed(c, n, idx, values, true); }
 extern "C" int vft_branch_lengths_scatter(vft_ctx *c, int64_t n, const int64_t *idx, const void *values) {
@@ -4008,42 +3944,30 @@ extern "C" int vft_posterior_profiles_blen(vft_ctx *c, int64_t n, const int64_t 
     if (int r = ensure_blen(c)) return r;
     if (int r = ensure_ml_rows(c)) return r;
     const size_t idB = (size_t) n * 8;
-    const bool smallIds = 7 * idB <= VFT_SMALL_BYTES;
-    char *s;
-    if (smallIds) {
-        char *h;
-        if (int r = io_alloc(c, 7 * idB, &h, &s)) return r;
-        memcpy(h, out, idB);
-        memcpy(h + idB, a, idB);
-        memcpy(h + 2 * idB, b, idB);
-        memcpy(h + 3 * idB, lenIdxA, idB);
-        memcpy(h + 4 * idB, lenIdxB, idB);
-    } else {
-        if (int r = ensure_scratch(c, 7 * idB + 512)) return r;
-        s = (char *) c->scratch;
-        HIPCHK(c, hipMemcpyAsync(s, out, idB, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(s + idB, a, idB, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(s + 2 * idB, b, idB, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(s + 3 * idB, lenIdxA, idB, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(s + 4 * idB, lenIdxB, idB, hipMemcpyHostToDevice, c->stream));
-    }
-    double *l1 = (double *) (s + 5 * idB), *l2 = (double *) (s + 6 * idB);
+    VftLayout L;   // five lists from the caller, two work arrays: the gathered lengths
+    const size_t oOut = L.add(idB), oA = L.add(idB), oB = L.add(idB), oIdxA = L.add(idB), oIdxB = L.add(idB), oLen1 = L.add(idB), oLen2 = L.add(idB);
+    Stage st;
+    if (int r = st.open(c, L.total(), VFT_SMALL_BYTES)) return r;
+    VFTCHK(st.put(oOut, out, idB));
+    VFTCHK(st.put(oA, a, idB));
+    VFTCHK(st.put(oB, b, idB));
+    VFTCHK(st.put(oIdxA, lenIdxA, idB));
+    VFTCHK(st.put(oIdxB, lenIdxB, idB));
+    double *l1 = st.dev<double>(oLen1), *l2 = st.dev<double>(oLen2);
     if (c->cfg.precision == 4)
-        launch((k_gather_lengths<float>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const float *) c->blen,
-               (const int64_t *) (s + 3 * idB), (const int64_t *) (s + 4 * idB), l1, l2, n);
+        launch((k_gather_lengths<float>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const float *) c->blen, st.dev<const int64_t>(oIdxA),
+               st.dev<const int64_t>(oIdxB), l1, l2, n);
     else
-        launch((k_gather_lengths<double>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double *) c->blen,
-               (const int64_t *) (s + 3 * idB), (const int64_t *) (s + 4 * idB), l1, l2, n);
+        launch((k_gather_lengths<double>), dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double *) c->blen, st.dev<const int64_t>(oIdxA),
+               st.dev<const int64_t>(oIdxB), l1, l2, n);
     // the results go to the nodes' dense ML rows: no stash, no tile commit
     const int64_t chunk = 32768;
     for (int64_t k0 = 0; k0 < n; k0 += chunk) {
         const int64_t cnt = n - k0 < chunk ? n - k0 : chunk;
-        launch_posterior_rows(c, cnt, (const int64_t *) s + k0, (const int64_t *) (s + idB) + k0, (const int64_t *) (s + 2 * idB) + k0, (const double *) l1 + k0,
-                              (const double *) l2 + k0);
+        launch_posterior_rows(c, cnt, st.dev<const int64_t>(oOut) + k0, st.dev<const int64_t>(oA) + k0, st.dev<const int64_t>(oB) + k0, l1 + k0, l2 + k0);
         LAUNCHCHK(c);
     }
-    if (!smallIds) HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VFT_OK;
+    return st.finish();
 }
 
 // n posteriorProfile calls in order in one launch (k_posterior_chain), lengths from the device's branchlength[];
@@ -4060,32 +3984,24 @@ static int posterior_chains(vft_ctx *c, int32_t nChains, const int32_t *chainOff
     }
     if (int r = ensure_blen(c)) return r;
     if (int r = ensure_ml_rows(c)) return r;
-    const size_t idB = (size_t) n * 8, dB = ((size_t) n + 7) & ~(size_t) 7, offB = chainOff ? (size_t) (nChains + 1) * 4 : 0;
-    char *h, *s;
-    if (int r = io_alloc(c, 5 * idB + dB + offB, &h, &s)) return r;
-    memcpy(h, out, idB);
-    memcpy(h + idB, a, idB);
-    memcpy(h + 2 * idB, b, idB);
-    memcpy(h + 3 * idB, lenIdxA, idB);
-    memcpy(h + 4 * idB, lenIdxB, idB);
-    uint8_t *direct = (uint8_t *) (h + 5 * idB);
-    for (int32_t ch = 0; ch < nChains; ch++) {
-        const int32_t k0 = chainOff ? chainOff[ch] : 0, k1 = chainOff ? chainOff[ch + 1] : n;
-        for (int32_t k = k0; k < k1; k++) {
-            uint8_t d = 0;
-            for (int32_t j = k0; j < k; j++) {
-                if (out[j] == a[k]) d |= 1;
-                if (out[j] == b[k]) d |= 2;
-            }
-            direct[k] = d;
-        }
-    }
-    if (chainOff) memcpy(h + 5 * idB + dB, chainOff, offB);
+    const size_t idB = (size_t) n * 8, offB = chainOff ? (size_t) (nChains + 1) * 4 : 0;
+    VftLayout L;
+    const size_t oOut = L.add(idB), oA = L.add(idB), oB = L.add(idB), oLenA = L.add(idB), oLenB = L.add(idB), oDirect = L.add((size_t) n),
+                 oOff = L.add(offB, 8);
+    Stage st;
+    if (int r = st.open(c, L.total(), Stage::RING_ONLY)) return r;
+    st.put(oOut, out, idB);
+    st.put(oA, a, idB);
+    st.put(oB, b, idB);
+    st.put(oLenA, lenIdxA, idB);
+    st.put(oLenB, lenIdxB, idB);
+    chain_direct_flags(st.host<uint8_t>(oDirect), nChains, chainOff, n, out, a, b);
+    if (chainOff) st.put(oOff, chainOff, offB);
     VFT_DISPATCH(c, launch((k_posterior_chain<REAL, NC>), dim3(cdiv(c->d.nPos, VFT_ML_WG), (unsigned) nChains), dim3(VFT_ML_WG), 0, c->stream,
-                           arena<REAL>(c), (const int64_t *) s, (const int64_t *) (s + idB), (const int64_t *) (s + 2 * idB),
-                           (const int64_t *) (s + 3 * idB), (const int64_t *) (s + 4 * idB), (const uint8_t *) (s + 5 * idB), n,
-                           (const REAL *) c->blen, c->minLen, c->minRel, chainOff ? (const int32_t *) (s + 5 * idB + dB) : nullptr));
-    if (!c->allRows) launch(k_mark_rows, dim3(cdiv(n, 64)), dim3(64), 0, c->stream, c->mlIs, (const int64_t *) s, n, c->d.nSeqs);
+                           arena<REAL>(c), st.dev<const int64_t>(oOut), st.dev<const int64_t>(oA), st.dev<const int64_t>(oB),
+                           st.dev<const int64_t>(oLenA), st.dev<const int64_t>(oLenB), st.dev<const uint8_t>(oDirect), n,
+                           (const REAL *) c->blen, c->minLen, c->minRel, chainOff ? st.dev<const int32_t>(oOff) : nullptr));
+    if (!c->allRows) launch(k_mark_rows, dim3(cdiv(n, 64)), dim3(64), 0, c->stream, c->mlIs, st.dev<const int64_t>(oOut), n, c->d.nSeqs);
     LAUNCHCHK(c);
     return VFT_OK;
 }
@@ -4122,7 +4038,7 @@ static inline int mlopt_cpt(const vft_ctx *c, bool &quad) {
 
 // workspaces of the line-search kernels for long alignments (vft_kernels_ml_long.h): nWG x stride bytes, grown as needed
 static int ensure_ml_long_ws(vft_ctx *c, size_t nWG, int nRows, size_t *stride) {
-    *stride = (vft_ml_long_ws_bytes(c->d.nPos, c->d.nCodes, c->rs, nRows) + 255) & ~(size_t) 255;
+    *stride = vft_pad256(vft_ml_long_ws_bytes(c->d.nPos, c->d.nCodes, c->rs, nRows));
     const size_t bytes = nWG * *stride;
     if (bytes <= c->mlLongWsBytes) return VFT_OK;
     return own_regrow(c, &c->mlLongWs, &c->mlLongWsBytes, bytes);
@@ -4182,14 +4098,16 @@ extern "C" int vft_ml_optimize_splits(vft_ctx *c, int64_t n, const int64_t *ids,
     const int cpt = mlopt_cpt(c, quad);
     const size_t idB = (size_t) n * 8;
     if (7 * idB > VFT_SMALL_BYTES) return fail(c, VFT_ERR_INVALID, "vft_ml_optimize_splits: too many splits per call");
-    char *h, *s;
-    if (int r = io_alloc(c, 7 * idB, &h, &s)) return r;
-    memcpy(h, ids, 3 * idB);
-    memcpy(h + 3 * idB, lenIdx, 3 * idB);
-    memcpy(h + 6 * idB, recompute, idB);
+    VftLayout L;
+    const size_t oIds = L.add(3 * idB), oLenIdx = L.add(3 * idB), oRec = L.add(idB);
+    Stage st;
+    if (int r = st.open(c, L.total(), Stage::RING_ONLY)) return r;
+    st.put(oIds, ids, 3 * idB);
+    st.put(oLenIdx, lenIdx, 3 * idB);
+    st.put(oRec, recompute, idB);
     int r = VFT_OK;
-    VFT_DISPATCH(c, (r = ml_optimize_launch<REAL, NC>(c, n, cpt, quad, (const int64_t *) s, (const int64_t *) (s + 3 * idB),
-                                                      (const int64_t *) (s + 6 * idB), ftol, atol)));
+    VFT_DISPATCH(c, (r = ml_optimize_launch<REAL, NC>(c, n, cpt, quad, st.dev<const int64_t>(oIds), st.dev<const int64_t>(oLenIdx),
+                                                      st.dev<const int64_t>(oRec), ftol, atol)));
     if (r) return r;
     LAUNCHCHK(c);
     return VFT_OK;
@@ -4251,16 +4169,18 @@ static int ml_quartet_nni(vft_ctx *c, int64_t n, const int64_t *ids, const int64
     const int cpt = mlopt_cpt(c, quad);
     const size_t idB = (size_t) n * 8, resB = (size_t) n * sizeof(QuartetNNIResult);
     static_assert(sizeof(QuartetNNIResult) == sizeof(vft_quartet_nni), "result record layout");
-    const size_t stB = ((size_t) n * sizeof(QuartetNNIState) + 255) & ~(size_t) 255;
+    VftLayout L, W;   // the call's lists and results (ring), the quartets' states (scratch)
+    const size_t oIds = L.add(4 * idB), oLenIdx = L.add(5 * idB), oRes = L.add(resB, 256);
+    W.add((size_t) n * sizeof(QuartetNNIState));
+    const size_t stB = W.add(0, 256);   // (padded: what the refusal has always counted)
     if (9 * idB + resB + stB > VFT_SMALL_BYTES) return fail(c, VFT_ERR_INVALID, "vft_ml_quartet_nni: too many quartets per call");
-    const size_t off = (9 * idB + 255) & ~(size_t) 255;
-    char *h, *s;
-    if (int r = io_alloc(c, off + ((resB + 255) & ~(size_t) 255), &h, &s)) return r;
-    memcpy(h, ids, 4 * idB);
-    memcpy(h + 4 * idB, lenIdx, 5 * idB);
-    if (int r = ensure_scratch(c, stB + 512)) return r;
-    QuartetNNIState *dState = (QuartetNNIState *) c->scratch;
-    const int64_t *dIds = (const int64_t *) s, *dLi = (const int64_t *) (s + 4 * idB);
+    Stage st, work;
+    if (int r = st.open(c, L.total(), Stage::RING_ONLY)) return r;
+    st.put(oIds, ids, 4 * idB);
+    st.put(oLenIdx, lenIdx, 5 * idB);
+    if (int r = work.open(c, W.total(), Stage::SCRATCH_ONLY)) return r;
+    QuartetNNIState *dState = work.dev<QuartetNNIState>(0);
+    const int64_t *dIds = st.dev<const int64_t>(oIds), *dLi = st.dev<const int64_t>(oLenIdx);
     // init -> {round (a workgroup per pairing) -> decide} x rounds -> verdict, all queued; one wait at the end
     const int nRounds = mlAccuracy < 2 ? 2 : mlAccuracy;
     // In mode 2 the quartet kernel uses its close_limit for the star-topology test alone ("is the internal branch worth more
@@ -4278,13 +4198,12 @@ static int ml_quartet_nni(vft_ctx *c, int64_t n, const int64_t *ids, const int64
         launch(k_ml_nni_decide, g1, b1, 0, c->stream, dState, n, c->minLen, closeLimit, (int) mlAccuracy, round == nRounds - 1 ? 1 : 0);
     }
     if (c->cfg.precision == 4)
-        launch((k_ml_nni_verdict<float>), g1, b1, 0, c->stream, (const QuartetNNIState *) dState, dLi, (float *) c->blen, (QuartetNNIResult *) (s + off), n);
+        launch((k_ml_nni_verdict<float>), g1, b1, 0, c->stream, (const QuartetNNIState *) dState, dLi, (float *) c->blen, st.dev<QuartetNNIResult>(oRes), n);
     else
-        launch((k_ml_nni_verdict<double>), g1, b1, 0, c->stream, (const QuartetNNIState *) dState, dLi, (double *) c->blen, (QuartetNNIResult *) (s + off), n);
+        launch((k_ml_nni_verdict<double>), g1, b1, 0, c->stream, (const QuartetNNIState *) dState, dLi, (double *) c->blen, st.dev<QuartetNNIResult>(oRes), n);
     LAUNCHCHK(c);
-    if (int w = wait_stream(c)) return w;
-    memcpy(results, h + off, resB);
-    return VFT_OK;
+    st.get(results, oRes, resB);
+    return st.finish(Stage::WAIT_STREAM);
 }
 
 extern "C" int vft_ml_quartet_nni(vft_ctx *c, int64_t n, const int64_t *ids, const int64_t *lenIdx, double ftol, double atol,
@@ -4326,14 +4245,14 @@ extern "C" int vft_ml_split_tests(vft_ctx *c, int64_t n, const int64_t *ids, con
     int64_t chunk = (int64_t) ((512u << 20) / ((size_t) 3 * nPos * sizeof(double)));
     chunk = chunk < 1 ? 1 : chunk > n ? n : chunk;
     const size_t idB = (size_t) chunk * 8;
-    const size_t colB = nBoot > 0 ? (((size_t) nBoot * nPos * 2 + 255) & ~(size_t) 255) : 0;
-    const size_t siteB = (size_t) chunk * 3 * nPos * sizeof(double);
     // scratch: ids[4] | lenIdx[5] | loglk[3] | lengths[10] | support[1] | colT | site
-    const size_t headB = (23 * idB + 255) & ~(size_t) 255;
-    if (int r = ensure_scratch(c, headB + colB + siteB + 512)) return r;
+    VftLayout W;
+    W.add(23 * idB);
+    const size_t oCol = W.add(nBoot > 0 ? (size_t) nBoot * nPos * 2 : 0, 256), oSite = W.add((size_t) chunk * 3 * nPos * sizeof(double), 256);
+    if (int r = ensure_scratch(c, W.total())) return r;
     char *s = (char *) c->scratch;
-    uint16_t *dCol = (uint16_t *) (s + headB);
-    double *dSite = (double *) (s + headB + colB);
+    uint16_t *dCol = (uint16_t *) (s + oCol);
+    double *dSite = (double *) (s + oSite);
     if (nBoot > 0) {
         std::vector<uint16_t> colT((size_t) nBoot * nPos);
         for (int32_t b = 0; b < nBoot; b++)
@@ -4418,15 +4337,15 @@ extern "C" int vft_split_supports(vft_ctx *c, int64_t n, const int64_t *a, const
     // buffer could not overflow (zero-distance quartets of near-duplicate sequences tie in all their resamples).
     const unsigned int flagCap = 1u << 22;   // 4M records = 235 MB
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t) flagCap / nBoot));
-    const size_t idB = (((size_t) chunk * 8) + 255) & ~(size_t) 255, colB = ((colT.size() * 4) + 255) & ~(size_t) 255;
-    const size_t cntB = (((size_t) chunk * 4) + 255) & ~(size_t) 255;
-    const size_t flagB = (size_t) flagCap * VFT_SUPPORT_REC * 8;
-    if (int r = ensure_scratch(c, 4 * idB + colB + cntB + 256 + flagB + 512)) return r;
-    char *s = (char *) c->scratch;
-    HIPCHK(c, hipMemcpyAsync(s + 4 * idB, colT.data(), colT.size() * 4, hipMemcpyHostToDevice, c->stream));
-    unsigned int *dCnt = (unsigned int *) (s + 4 * idB + colB);
-    unsigned int *dNFlag = (unsigned int *) (s + 4 * idB + colB + cntB);
-    double *dFlag = (double *) (s + 4 * idB + colB + cntB + 256);
+    VftLayout W;
+    const size_t oA = W.add((size_t) chunk * 8, 256), oB = W.add((size_t) chunk * 8, 256), oC = W.add((size_t) chunk * 8, 256),
+                 oD = W.add((size_t) chunk * 8, 256), oCol = W.add(colT.size() * 4, 256), oCnt = W.add((size_t) chunk * 4, 256),
+                 oNFlag = W.add(4, 256), oFlag = W.add((size_t) flagCap * VFT_SUPPORT_REC * 8, 256);
+    Stage st;
+    if (int r = st.open(c, W.total(), Stage::SCRATCH_ONLY)) return r;
+    VFTCHK(st.put(oCol, colT.data(), colT.size() * 4));
+    unsigned int *dCnt = st.dev<unsigned int>(oCnt), *dNFlag = st.dev<unsigned int>(oNFlag);
+    double *dFlag = st.dev<double>(oFlag);
     const int32_t scoredist = (c->cfg.n_codes == 4 && !c->hasDm) ? 0 : 1;   // logCorrect's choice, NJ.tcc:324
     // margins below eps are decided on the host with its own libm (the device's log may differ in the last bit);
     // a distance is < 3, so errors of a few 1e-16 cannot reach 1e-9
@@ -4444,16 +4363,16 @@ extern "C" int vft_split_supports(vft_ctx *c, int64_t n, const int64_t *a, const
     std::vector<double> rec;
     for (int64_t k0 = 0; k0 < n; k0 += chunk) {
         const int64_t m = std::min<int64_t>(chunk, n - k0);
-        HIPCHK(c, hipMemcpyAsync(s, a + k0, (size_t) m * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(s + idB, b + k0, (size_t) m * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(s + 2 * idB, cc + k0, (size_t) m * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(s + 3 * idB, d + k0, (size_t) m * 8, hipMemcpyHostToDevice, c->stream));
+        VFTCHK(st.put(oA, a + k0, (size_t) m * 8));
+        VFTCHK(st.put(oB, b + k0, (size_t) m * 8));
+        VFTCHK(st.put(oC, cc + k0, (size_t) m * 8));
+        VFTCHK(st.put(oD, d + k0, (size_t) m * 8));
         HIPCHK(c, hipMemsetAsync(dNFlag, 0, 4, c->stream));
         if (pairs) HIPCHK(c, hipMemsetAsync(dCnt, 0, (size_t) m * 4, c->stream));   // the long kernel adds to its counts
 #define VFT_SUPPORT_LAUNCH(KERNEL, WG)                                                                                        \
-    launch((KERNEL), dim3((unsigned) m), dim3(WG), lds, c->stream, arena<REAL>(c), (const int64_t *) s,                        \
-           (const int64_t *) (s + idB), (const int64_t *) (s + 2 * idB), (const int64_t *) (s + 3 * idB), m,                   \
-           (const int32_t *) (s + 4 * idB), nBoot, scoredist, eps, dCnt, dNFlag, dFlag, flagCap)
+    launch((KERNEL), dim3((unsigned) m), dim3(WG), lds, c->stream, arena<REAL>(c), st.dev<const int64_t>(oA),                  \
+           st.dev<const int64_t>(oB), st.dev<const int64_t>(oC), st.dev<const int64_t>(oD), m,                                 \
+           st.dev<const int32_t>(oCol), nBoot, scoredist, eps, dCnt, dNFlag, dFlag, flagCap)
         VFT_DISPATCH(c, {
             if (pairs == 3) VFT_SUPPORT_LAUNCH((k_split_support_long<REAL, NC, 3>), VFT_SUPPORT_LONG_WG);
             else if (pairs == 2) VFT_SUPPORT_LAUNCH((k_split_support_long<REAL, NC, 2>), VFT_SUPPORT_LONG_WG);
@@ -4532,14 +4451,13 @@ extern "C" int vft_debug_option(vft_ctx *c, int32_t option, int64_t value) {
 extern "C" int vft_debug_log(vft_ctx *c, int64_t n, const double *x, double *out) {
     if (!c || n < 0 || !x || !out) return VFT_ERR_INVALID;
     if (n == 0) return VFT_OK;
-    if (int r = ensure_scratch(c, (size_t) n * 16)) return r;
-    double *dx = (double *) c->scratch, *dy = dx + n;
-    HIPCHK(c, hipMemcpyAsync(dx, x, (size_t) n * 8, hipMemcpyHostToDevice, c->stream));
-    launch(k_debug_log, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, (const double *) dx, dy, n);
+    Stage st;
+    if (int r = st.open(c, (size_t) n * 16, Stage::SCRATCH_ONLY)) return r;
+    VFTCHK(st.put(0, x, (size_t) n * 8));
+    launch(k_debug_log, dim3(cdiv(n, 256)), dim3(256), 0, c->stream, st.dev<const double>(0), st.dev<double>((size_t) n * 8), n);
     LAUNCHCHK(c);
-    HIPCHK(c, hipMemcpyAsync(out, dy, (size_t) n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return VFT_OK;
+    st.get(out, (size_t) n * 8, (size_t) n * 8);
+    return st.finish();
 }
 
 // ---------------------------------------------------------------------------------------------- timing
