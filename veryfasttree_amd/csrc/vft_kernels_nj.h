@@ -79,7 +79,16 @@ __global__ void k_extract_query(Arena<REAL> A, int64_t node, QueryBuf<REAL> q) {
 // vectors also go, as query number mqIdx, into the group's INTERLEAVED buffer: per column VFT_MQ_STRIDE(S) = 4 S + 4 numbers,
 // [f of query 0 (4)] ... [f of query S-1 (4)] [w of queries 0..S-1, padded to 4] - one base pointer and two or three scalar loads
 // per column for all S queries, where S separate buffers took 2 S pointers (SGPR pairs the kernel has no room for) and 2 S loads.
+// Behind the weights: [one dword with the S queries' reference codes, a byte each, padded to 4 numbers] - what tells
+// vft_int_chunk_consume_prof that a query's column is a plain code (its vector the exact one-hot of that code).
+// -DVFT_NO_PLAIN_COLUMNS (a variant build, for A/B runs) compiles the plain-column path and the skip of pure padding groups out.
+#ifdef VFT_NO_PLAIN_COLUMNS
+#define VFT_PLAIN_COLUMNS 0
 #define VFT_MQ_STRIDE(S) (4 * (S) + 4)
+#else
+#define VFT_PLAIN_COLUMNS 1
+#define VFT_MQ_STRIDE(S) (4 * (S) + 8)
+#endif
 template <typename REAL>
 struct QuerySlot {
     int64_t node;
@@ -98,6 +107,7 @@ __global__ void k_extract_query_batch(Arena<REAL> A, const QuerySlot<REAL> *qs) 
 #pragma unroll
             for (int k = 0; k < 4; k++) dst[4 * sl.mqIdx + k] = sl.q.f[p * 4 + k];
             dst[4 * sl.mqS + sl.mqIdx] = sl.q.w[p];
+            if (VFT_PLAIN_COLUMNS) ((uint8_t *) (dst + 4 * sl.mqS + 4))[sl.mqIdx] = sl.q.code[p];
         }
     }
 }
@@ -625,10 +635,10 @@ struct IntChunkAll {
 // OR-ed onto the implied value - so that no load sits in a branch and two column groups can alternate with exact wait counters:
 // 142 -> 172-220 us per pass of four seeds.  Most (tile, column) pairs have no vector lane at all and the branch skips the
 // instruction; issued unconditionally, the 128-bit loads cost the texture path more than the exposed latency they hide.)
+// p0: the group's first column; codes / byte0: the target's code bytes of the group are bytes byte0 .. byte0 + SUB - 1 of `codes`
 template <typename REAL, int SUB>
-__device__ __forceinline__ void vft_int_chunk_load_all(IntChunkAll<REAL, SUB> &r, int c, int sub, const uint4 codes, const REAL *wT,
+__device__ __forceinline__ void vft_int_chunk_load_all(IntChunkAll<REAL, SUB> &r, int64_t p0, const uint4 codes, int byte0, const REAL *wT,
                                                        vft_smask_t mM, vft_soff_t mO, const REAL *fT) {
-    const int64_t p0 = (int64_t) c * VFT_CHUNK + sub * SUB;
     vft_u4_t mk[SUB];
     vft_u2_t of[SUB];
 #pragma unroll
@@ -644,7 +654,7 @@ __device__ __forceinline__ void vft_int_chunk_load_all(IntChunkAll<REAL, SUB> &r
         const bool hw = __builtin_amdgcn_inverse_ballot_w64(mw);
         const uint32_t slotV = __builtin_amdgcn_mbcnt_hi(mk[b].y, __builtin_amdgcn_mbcnt_lo(mk[b].x, of[b].x));
         const uint32_t slotW = __builtin_amdgcn_mbcnt_hi(mk[b].w, __builtin_amdgcn_mbcnt_lo(mk[b].z, of[b].y));
-        const uint32_t cd = vft_byte(codes, sub * SUB + b);
+        const uint32_t cd = vft_byte(codes, byte0 + b);
         r.w[b] = (hv || cd != VFT_NOCODE_) ? (REAL) 1 : (REAL) 0;   // implicit weight (vft_layout.h)
         const char *wB = (const char *) wT, *fB = (const char *) fT;
         if (hw) r.w[b] = *(const REAL *) (wB + slotW * (uint32_t) sizeof(REAL));
@@ -732,6 +742,54 @@ __device__ __forceinline__ void vft_int_chunk_consume_all(const IntChunkAll<REAL
     }
 }
 
+// THE COLUMN LOOP of the multi-seed kernels for one internal target (the lane's; tile = its tile): a group of SUB = 8 columns is decoded
+// (vft_int_chunk_load_all) and handed to consume(ca, p0), group after group in column order.
+// PADDING GROUPS.  The columns [nPos, nChunk * 16) are padding: weight 0 on both sides, so a group that lies wholly there adds +0.0 to
+// every running sum - the identity (vft_int_chunk_consume) - and is left out: the loop runs over the groups that hold a column below
+// nPos, ONE group per trip, on that count alone.  At nPos = 200 that is 25 groups of 26.  The lane's 8 code bytes of group g are one
+// half of its 16-byte chunk - uint2 number 2 * (chunk * 64 + lane) + (g & 1) of the tile's codes - and are loaded one group ahead.
+// (A chunk per trip with a test in front of its second group, the obvious way: the branch in the middle of the body costs the scalar
+// registers their balance - 100 to 230 v_writelane / v_readlane inside the loops of all three kernels, tools/isa_loops.py.)
+// -DVFT_NO_PLAIN_COLUMNS: a chunk (two groups) per trip, padding included, as before.
+template <typename REAL, int SUB, typename F>
+__device__ __forceinline__ void vft_for_column_groups(const Arena<REAL> &A, int64_t tile, int lane, F consume) {
+    static_assert(SUB == 8, "a group is half a chunk of codes");
+    const int64_t pt = (int64_t) __builtin_amdgcn_readfirstlane((int) (tile - A.d.firstProfTile));
+    const uint4 *cT = A.profC + vft_c_idx(A.d, pt, 0, 0);
+    const vft_smask_t mM = (vft_smask_t) (A.colMask + vft_meta_idx(A.d, pt, 0));
+    const vft_soff_t mO = (vft_soff_t) (A.colOff + vft_meta_idx(A.d, pt, 0));
+    const REAL *wT = A.profW + vft_wstream_base(A.d, pt);
+    const REAL *fT = A.profF + vft_fstream_base(A.d, pt);
+    IntChunkAll<REAL, SUB> ca;
+#if VFT_PLAIN_COLUMNS
+    const uint2 *gT = (const uint2 *) cT + 2 * lane;
+    const int nGroup = (int) ((A.d.nPos + SUB - 1) / SUB);   // (<= 2 nChunk: every read stays inside the tile's codes)
+    uint2 cur = gT[0];
+    for (int g = 0; g < nGroup; g++) {
+        const int64_t p0 = (int64_t) g * SUB;
+        vft_int_chunk_load_all<REAL, SUB>(ca, p0, make_uint4(cur.x, cur.y, 0, 0), 0, wT, mM, mO, fT);
+        const int gn = g + 1 < nGroup ? g + 1 : g;
+        const uint2 nxt = gT[(int64_t) (gn >> 1) * (2 * VFT_TILE) + (gn & 1)];
+        consume(ca, p0);
+        cur = nxt;
+    }
+#else
+    uint4 cur = cT[lane];
+    const int nChunk = A.d.nChunk;
+    for (int c = 0; c < nChunk; c++) {
+        uint4 nxt;
+#pragma unroll
+        for (int sub = 0; sub < VFT_CHUNK / SUB; sub++) {
+            const int64_t p0 = (int64_t) c * VFT_CHUNK + sub * SUB;
+            vft_int_chunk_load_all<REAL, SUB>(ca, p0, cur, sub * SUB, wT, mM, mO, fT);
+            if (sub == 0) nxt = cT[(int64_t) (c + 1 < nChunk ? c + 1 : c) * VFT_TILE + lane];
+            consume(ca, p0);
+        }
+        cur = nxt;
+    }
+#endif
+}
+
 template <typename REAL, int S>
 __global__ __launch_bounds__(VFT_WG) void k_sweep_nt_leafq_multi(Arena<REAL> A, MultiLeafQ<REAL, S> M, SweepArgs s) {
     constexpr int SUB = 8;   // (groups of 4 columns: 142 -> 152 us per pass of four seeds)
@@ -779,29 +837,12 @@ __global__ __launch_bounds__(VFT_WG) void k_sweep_nt_leafq_multi(Arena<REAL> A, 
             double top[S], denom[S];
 #pragma unroll
             for (int q = 0; q < S; q++) top[q] = denom[q] = 0;
-            const int64_t pt = (int64_t) __builtin_amdgcn_readfirstlane((int) (tile - A.d.firstProfTile));
-            const uint4 *cT = A.profC + vft_c_idx(A.d, pt, 0, 0);
-            const vft_smask_t mM = (vft_smask_t) (A.colMask + vft_meta_idx(A.d, pt, 0));
-            const vft_soff_t mO = (vft_soff_t) (A.colOff + vft_meta_idx(A.d, pt, 0));
-            const REAL *wT = A.profW + vft_wstream_base(A.d, pt);
-            const REAL *fT = A.profF + vft_fstream_base(A.d, pt);
-            uint4 cur = cT[lane];
-            const int nChunk = A.d.nChunk;
-            constexpr int NSUB = VFT_CHUNK / SUB;
-            IntChunkAll<REAL, SUB> ca;
             const uint8_t *code[S];
 #pragma unroll
             for (int q = 0; q < S; q++) code[q] = M.Q[q].code;
-            for (int c = 0; c < nChunk; c++) {
-                uint4 nxt;
-#pragma unroll
-                for (int sub = 0; sub < NSUB; sub++) {
-                    vft_int_chunk_load_all<REAL, SUB>(ca, c, sub, cur, wT, mM, mO, fT);
-                    if (sub == 0) nxt = cT[(int64_t) (c + 1 < nChunk ? c + 1 : c) * VFT_TILE + lane];
-                    vft_int_chunk_consume_all<REAL, S, SUB>(ca, (int64_t) c * VFT_CHUNK + sub * SUB, code, top, denom);
-                }
-                cur = nxt;
-            }
+            vft_for_column_groups<REAL, SUB>(A, tile, lane, [&](const IntChunkAll<REAL, SUB> &ca, int64_t p0) {
+                vft_int_chunk_consume_all<REAL, S, SUB>(ca, p0, code, top, denom);
+            });
 #pragma unroll
             for (int q = 0; q < S; q++) {
                 weight[q] = (REAL) (denom[q] > 0 ? denom[q] : 0.01);
@@ -838,15 +879,25 @@ __device__ __forceinline__ void vft_pin_sums(double *top, double *denom) {
     for (int q = 0; q < S; q++) asm volatile("" : "+v"(top[q]), "+v"(denom[q]));
 }
 
+// PLAIN COLUMNS.  A query column that holds a plain code c (vft_extract_query: code != NOCODE; its weight is 1 or, where one child
+// had a gap, smaller) has the exact one-hot of c as its vector, so of the four products one is 1 * f_t[c] = f_t[c] and three are
+// +0 * f_t[k] = +0 (f_t is finite and not negative), and subtracting +0.0 from a double is the identity:
+//     (((1 - pr.x) - pr.y) - pr.z) - pr.w   is bit for bit   1.0 - (double) f_t[c]
+// - the leaf seed's formula (vft_int_chunk_consume_all) with ww = wq * w_t kept as it is; vft_query_tab and MODE_CRIT_LEAFQ rest on
+// the same identity.  The codes are wave-uniform (a byte per query in the column's record, VFT_MQ_STRIDE): one scalar branch per
+// (query, column) picks the short form - three uniform selects, one conversion, one subtraction - over two packed products, four
+// conversions and four subtractions.  Most columns of a profile seed are plain (sibling profiles mostly agree).
 template <typename REAL, int S>
 struct QueryCol {
     REAL w[S];
     typename UVec4<REAL>::type f[S];
+    uint32_t codes;   // byte q: query q's reference code at this column (VFT_PLAIN_COLUMNS)
 };
 template <typename REAL, int S>
 __device__ __forceinline__ void vft_query_col_load(QueryCol<REAL, S> &c, const REAL *mq, int64_t p) {
     const REAL *src = mq + p * VFT_MQ_STRIDE(S);
     const typename UVec4<REAL>::type wv = vft_uniform_load4<REAL>(src + 4 * S);
+    if (VFT_PLAIN_COLUMNS) c.codes = vft_uniform_load<uint32_t>((const uint32_t *) (src + 4 * S + 4));
 #pragma unroll
     for (int q = 0; q < S; q++) {
         c.w[q] = q == 0 ? wv.x : q == 1 ? wv.y : q == 2 ? wv.z : wv.w;
@@ -866,13 +917,30 @@ __device__ __forceinline__ void vft_int_chunk_consume_prof(const IntChunkAll<REA
         for (int q = 0; q < S; q++) {
             const REAL ww = cur.w[q] * ca.w[b];   // numeric_t product, NJ.tcc:1176
             const double wgt = (double) ww;
-            const typename UVec4<REAL>::type pr = cur.f[q] * ca.f[b];   // the four numeric_t products of NJ.tcc:933-937
-            double piece = 1.0 - (double) pr.x;
-            piece -= (double) pr.y;
-            piece -= (double) pr.z;
-            piece -= (double) pr.w;
+            // piece = head - (double) last.  Plain code cq: 1.0 - f_t[cq].  Otherwise ((1 - pr.x) - pr.y) - pr.z, then - pr.w.
+            // (a plain code is 0..3, NOCODE - a vector or a gap - is 127: bit 6 of the query's byte tells them apart.  An `if`
+            // without an `else` is one forward scalar branch; with two arms the structurised loop pays a flag and two more branches.
+            // So the selects run for a vector column too - there cq & 3 = 3 picks f_t[3], replaced at once.)
+            double head = 1.0;
+            REAL last;
+            if (VFT_PLAIN_COLUMNS) {
+                const unsigned long long m0 = (cur.codes & (1u << (8 * q))) ? ~0ull : 0ull, m1 = (cur.codes & (2u << (8 * q))) ? ~0ull : 0ull;
+                last = vft_usel(vft_usel(ca.f[b].x, ca.f[b].y, m0), vft_usel(ca.f[b].z, ca.f[b].w, m0), m1);   // f_t[cq]
+            }
+            // (told to be the rare case, the vector arm is laid out behind the loop body: a plain column falls through, no branch taken)
+            if (!VFT_PLAIN_COLUMNS || __builtin_expect((cur.codes & (0x40u << (8 * q))) != 0, 0)) {   // wave-uniform: a scalar branch
+                const typename UVec4<REAL>::type pr = cur.f[q] * ca.f[b];   // the four numeric_t products of NJ.tcc:933-937
+                head = 1.0 - (double) pr.x;
+                head -= (double) pr.y;
+                head -= (double) pr.z;
+                last = pr.w;
+            }
+            const double piece = head - (double) last;
             denom[q] += wgt;
             top[q] += wgt * piece;
+            // (the branch ends a basic block per query: without this the sums' arithmetic sinks below the column's last branch and
+            // every query's head / last / weight stays live until there - see vft_pin_sums)
+            if (VFT_PLAIN_COLUMNS) asm volatile("" : "+v"(top[q]), "+v"(denom[q]));
         }
         __builtin_amdgcn_sched_barrier(0);
         if (b + 1 < SUB) cur = nxt;
@@ -1123,26 +1191,10 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
     const VFT_KARG MultiLeafQ<REAL, S> *M1 = vft_kernarg<MultiLeafQ<REAL, S>>(offM);
     if (work) {   // (an internal node: the leaves of a profile query belong to the table workgroups - or, without any, do not exist in [heavyLo, hi))
         const REAL *mq = M1->mq;
-        const int64_t pt = (int64_t) __builtin_amdgcn_readfirstlane((int) (tile - A.d.firstProfTile));
-        const uint4 *cT = A.profC + vft_c_idx(A.d, pt, 0, 0);
-        const vft_smask_t mM = (vft_smask_t) (A.colMask + vft_meta_idx(A.d, pt, 0));
-        const vft_soff_t mO = (vft_soff_t) (A.colOff + vft_meta_idx(A.d, pt, 0));
-        const REAL *wT = A.profW + vft_wstream_base(A.d, pt);
-        const REAL *fT = A.profF + vft_fstream_base(A.d, pt);
-        uint4 cur = cT[lane];
-        const int nChunk = A.d.nChunk;
-        IntChunkAll<REAL, SUB> ca;
-        for (int c = 0; c < nChunk; c++) {
-            uint4 nxt;
-#pragma unroll
-            for (int sub = 0; sub < VFT_CHUNK / SUB; sub++) {
-                vft_int_chunk_load_all<REAL, SUB>(ca, c, sub, cur, wT, mM, mO, fT);
-                if (sub == 0) nxt = cT[(int64_t) (c + 1 < nChunk ? c + 1 : c) * VFT_TILE + lane];
-                vft_int_chunk_consume_prof<REAL, S, SUB>(ca, (int64_t) c * VFT_CHUNK + sub * SUB, mq, top, denom);
-                vft_pin_sums<S>(top, denom);
-            }
-            cur = nxt;
-        }
+        vft_for_column_groups<REAL, SUB>(A, tile, lane, [&](const IntChunkAll<REAL, SUB> &ca, int64_t p0) {
+            vft_int_chunk_consume_prof<REAL, S, SUB>(ca, p0, mq, top, denom);
+            vft_pin_sums<S>(top, denom);
+        });
     }
     const VFT_KARG MultiLeafQ<REAL, S> *Mk = vft_kernarg<MultiLeafQ<REAL, S>>(offM);   // after the loop: the epilogue's
     if (work) {
@@ -1290,31 +1342,14 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
         const uint8_t *code[SL];
 #pragma unroll
         for (int q = 0; q < SL; q++) code[q] = M1->L.Q[q].code;
-        const int64_t pt = (int64_t) __builtin_amdgcn_readfirstlane((int) (tile - A.d.firstProfTile));
-        const uint4 *cT = A.profC + vft_c_idx(A.d, pt, 0, 0);
-        const vft_smask_t mM = (vft_smask_t) (A.colMask + vft_meta_idx(A.d, pt, 0));
-        const vft_soff_t mO = (vft_soff_t) (A.colOff + vft_meta_idx(A.d, pt, 0));
-        const REAL *wT = A.profW + vft_wstream_base(A.d, pt);
-        const REAL *fT = A.profF + vft_fstream_base(A.d, pt);
-        uint4 cur = cT[lane];
-        const int nChunk = A.d.nChunk;
-        IntChunkAll<REAL, SUB> ca;
-        for (int c = 0; c < nChunk; c++) {
-            uint4 nxt;
-#pragma unroll
-            for (int sub = 0; sub < VFT_CHUNK / SUB; sub++) {
-                const int64_t p0 = (int64_t) c * VFT_CHUNK + sub * SUB;
-                vft_int_chunk_load_all<REAL, SUB>(ca, c, sub, cur, wT, mM, mO, fT);
-                if (sub == 0) nxt = cT[(int64_t) (c + 1 < nChunk ? c + 1 : c) * VFT_TILE + lane];
-                vft_int_chunk_consume_prof<REAL, SP, SUB>(ca, p0, mq, topP, denomP);
-                vft_pin_sums<SP>(topP, denomP);
-                __builtin_amdgcn_sched_barrier(0);   // one kind's query scalars live at a time: mq columns, then code bytes
-                vft_int_chunk_consume_all<REAL, SL, SUB, true>(ca, p0, code, topL, denomL);
-                vft_pin_sums<SL>(topL, denomL);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            cur = nxt;
-        }
+        vft_for_column_groups<REAL, SUB>(A, tile, lane, [&](const IntChunkAll<REAL, SUB> &ca, int64_t p0) {
+            vft_int_chunk_consume_prof<REAL, SP, SUB>(ca, p0, mq, topP, denomP);
+            vft_pin_sums<SP>(topP, denomP);
+            __builtin_amdgcn_sched_barrier(0);   // one kind's query scalars live at a time: mq columns, then code bytes
+            vft_int_chunk_consume_all<REAL, SL, SUB, true>(ca, p0, code, topL, denomL);
+            vft_pin_sums<SL>(topL, denomL);
+            __builtin_amdgcn_sched_barrier(0);
+        });
     }
     const VFT_KARG MixedQ<REAL, SL, SP> *Mk = vft_kernarg<MixedQ<REAL, SL, SP>>(offsetof(Args, M));   // after the loop: the epilogue's
     if (work) {
