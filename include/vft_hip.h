@@ -100,6 +100,16 @@ int vft_set_distance_matrix(vft_ctx *ctx, const void *distances, const void *cod
    one being the NOCODE (gap) row.  Passing NULLs selects Jukes-Cantor (nt only). */
 int vft_set_transition_matrix(vft_ctx *ctx, const void *stat, const void *statinv, const void *eigenval,
                               const void *codefreq, const void *eigeninv, const void *eigeninvT);
+/* `-approxml` (options.exactML == false, NJ.tcc:2390-2421): the near-constant posterior tables nearP / nearFreq of the transition
+   matrix set last (TransitionMatrix.tcc:227-279), nCodes x nCodes row-major numeric_t each.  20 states only: tables given to a 4-state
+   context are refused.  vft_set_transition_matrix clears them - a new matrix has new tables.  NULL, NULL clears them too. */
+int vft_set_near_posteriors(vft_ctx *ctx, const void *near_p, const void *near_freq);
+/* The switch, off by default.  The posteriors (vft_posterior_*, and those inside vft_ml_optimize_splits, vft_ml_quartet_nni*,
+   vft_ml_split_tests) take the approximate branch only with 20 states, the switch on and the tables present; with the switch on, a
+   20-state matrix model and no tables they fail (VFT_ERR_STATE) instead of running exact.  A 4-state context accepts the switch
+   and ignores it, as the reference does under -nt.  vft_get_approx_ml returns the switch (0 / 1). */
+int vft_set_approx_ml(vft_ctx *ctx, int32_t on);
+int vft_get_approx_ml(vft_ctx *ctx);
 /* Rate categories (NJ.h Rates: rates[n_rates], ratecat[n_pos]). */
 int vft_set_rates(vft_ctx *ctx, const void *rates, int32_t n_rates, const int64_t *ratecat);
 /* ML tolerances that the reference reads from Options inside the hot loops (Constants.h:26-39). */

@@ -319,6 +319,9 @@ int vft_gtr_tables(const double *rates, const double *freq, int32_t precision, d
    C ABI themselves. */
 int vft_aa_model_tables(int32_t model, int32_t precision, double *stat, double *statinv, double *eigenval, double *codefreq,
                         double *eigeninv, double *eigeninvT);
+/* nearP[20][20] / nearFreq[20][20] of a built-in model (TransitionMatrix.tcc:227-279), what the driver hands to
+   vft_set_near_posteriors beside the model for `-approxml`: numeric_t values held in double.  No device. */
+int vft_aa_near_tables(int32_t model, int32_t precision, double *near_p, double *near_freq);
 /* The default protein distance matrix (matrixBLOSUM45 + setupDistanceMatrix, DistanceMatrix.tcc:33-36, 102-155):
    distances[20][20], codefreq[20][20], eigenval[20], eigentot[20] as vft_set_distance_matrix takes them. */
 int vft_blosum45_tables(int32_t precision, double *distances, double *codefreq, double *eigenval, double *eigentot);

@@ -10,6 +10,7 @@ or - with -mllen - the tree of `VeryFastTree -nt -nome -mllen [-nocat | -cat N] 
     python tools/nj_tree.py in.fasta -intree start.nwk [-mllen ... | -full ...] > tree.nwk   # `VeryFastTree -intree start.nwk ...`: no NJ phase
     python tools/nj_tree.py in.fasta [any mode above] -pseudo [W] > tree.nwk   # `VeryFastTree ... -pseudo [W]`: pseudocount distances
     python tools/nj_tree.py in.fasta -full -spr 4 -mlacc 2 -slownni [-nni N] [-mlnni N] [-sprlength N] > tree.nwk   # the thorough search
+    python tools/nj_tree.py in.fasta -aa [-wag | -lg] -full|-mllen -approxml > tree.nwk   # `VeryFastTree ... -approxml` (alias -mlapprox)
     python tools/nj_tree.py -makematrix [-rawdist] [-aa] [-double] in.fasta > matrix.txt   # `VeryFastTree [-nt] [-rawdist] [-double-precision] -makematrix`
 
 Neighbour joining with top hits on the device (veryfasttree_amd/host/NJDriver.h), the root, minimum-evolution branch
@@ -37,6 +38,9 @@ dropped early, N rounds of the -gtr fit, the supports' second pass always (also 
 subtree is skipped in any NNI round.  -nni N / -mlnni N: N minimum-evolution / ML NNI rounds instead of round(4 log2 n) / round(2 log2 n);
 -nni 0 also means -spr 0, -mlnni 0 is -noml.  -sprlength N: SPR chains of at most N steps (default 10, at most 64).  Given without -full
 they end the program with a message.
+-approxml (or -mlapprox): the reference's option of that name - the posteriors of a protein run's ML stages skip the rotation where one
+state dominates and the rest follows the model's near-constant table (NJ.tcc:2390-2421).  Accepted and without effect for nucleotides
+and where no ML stage runs, as in the reference.
 -boot N: N resamples instead of 1000 for the supports, local (default mode) and SH-like (-mllen, -full) alike, as the reference's
 -boot; -boot 0 is -nosupport.  Local supports take every alignment the NJ phase takes (10 240 columns).
 -full, -mllen, -double, -aa / -jtt and -nj-lengths are this tool's own words; every other flag is the reference's and means what

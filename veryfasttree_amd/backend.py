@@ -29,7 +29,7 @@ I32 = C.c_int32
 
 EXPORTS = [
     "vft_device_malloc", "vft_device_free", "vft_device_upload", "vft_create", "vft_destroy", "vft_allocation_count", "vft_last_error", "vft_set_stream", "vft_synchronize", "vft_upload_leaves",
-    "vft_set_distance_matrix", "vft_set_transition_matrix", "vft_set_rates", "vft_set_ml_limits", "vft_set_jc_exact", "vft_set_parents",
+    "vft_set_distance_matrix", "vft_set_transition_matrix", "vft_set_rates", "vft_set_ml_limits", "vft_set_jc_exact", "vft_set_near_posteriors", "vft_set_approx_ml", "vft_get_approx_ml", "vft_set_parents",
     "vft_set_node_scalars", "vft_get_node_scalars", "vft_set_out_distances", "vft_get_out_distances", "vft_out_distance_mirror", "vft_set_max_node",
     "vft_profile_upload", "vft_profile_download", "vft_profile_nvectors", "vft_average_profiles", "vft_out_profile_full", "vft_out_profile_partial", "vft_out_profile_finish",
     "vft_out_profile_update", "vft_out_profile_upload", "vft_out_profile_download", "vft_out_distances", "vft_sweep",
@@ -55,7 +55,7 @@ HIT_F64 = np.dtype([("j", np.int64), ("dist", np.float64), ("weight", np.float64
 
 HOST_LIB_PATH = os.path.join(LIB_DIR, "libvft_host.so")
 HOST_EXPORTS = ["vft_nj_run", "vft_nj_newick", "vft_nj_ml_newick", "vft_nj_last_join_crcs", "vft_nj_last_stage_seconds", "vft_nj_last_walk_dual", "vft_nj_last_lane_exchange", "vft_nj_lane_share", "vft_nj_out_profile_block", "vft_nj_last_gamma", "vft_nj_round_plan", "vft_nj_make_matrix", "vft_tree_partitioning", "vft_knuth_stream", "vft_ml_lengths", "vft_gtr_tables",
-                "vft_aa_model_tables", "vft_blosum45_tables", "vft_aa_model_as_distance_tables"]
+                "vft_aa_model_tables", "vft_aa_near_tables", "vft_blosum45_tables", "vft_aa_model_as_distance_tables"]
 
 
 class _NJOptions(C.Structure):
@@ -247,6 +247,17 @@ def aa_model_tables(model, dtype=np.float32):
     return out
 
 
+def aa_near_tables(model, dtype=np.float32):
+    """`-approxml`'s near-constant posteriors of the built-in amino-acid model `model` as the host driver builds them
+    (vft_aa_near_tables, host/AAModels.h; no device): dict of nearP[20,20], nearFreq[20,20] - numeric_t values in double."""
+    lib = load_host_library()
+    out = dict(nearP=np.zeros((20, 20)), nearFreq=np.zeros((20, 20)))
+    rc = lib.vft_aa_near_tables(I32(AA_MODELS[model]), I32(np.dtype(dtype).itemsize), _ptr(out["nearP"]), _ptr(out["nearFreq"]))
+    if rc != 0:
+        raise VftError("vft_aa_near_tables failed")
+    return out
+
+
 def distance_tables(model=None, dtype=np.float32):
     """model None: the BLOSUM45-derived distance matrix (vft_blosum45_tables); else the model's transition matrix in the
     distance-matrix slots (vft_aa_model_as_distance_tables).  dict of distances, codefreq [20,20], eigenval, eigentot."""
@@ -282,8 +293,10 @@ def uniquify(codes):
 def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtype=np.float32, me_lengths=False,
               unique=None, scoredist=False, n_bootstrap=0, mllen=0, return_loglk=False, return_rates=False, me_nni=False, ml_nni=0, spr=0, gtr=False, return_gtr=False,
               aa_model=None, comm=None, threads=1, debug_flags=0, gamma=False, out_profile_parts=0, slow=False, intree=None, pseudo=0.0,
-              ml_accuracy=1, slow_nni=False, nni_rounds=None, ml_nni_rounds=None, spr_length=None):
+              ml_accuracy=1, slow_nni=False, nni_rounds=None, ml_nni_rounds=None, spr_length=None, approx_ml=False):
     """The NJ phase of the whole alignment `codes_all` (duplicates included) as the reference's "NJ" tree string.
+    approx_ml: `-approxml` - the ML stages' posteriors of a protein run take the near-constant approximation where it holds; no member
+    of vft_nj_options but state of the context: ops.set_approx_ml(True) on what make_ops returns, before the driver runs.
     intree (str): `-intree` - Newick text of a starting tree; the NJ phase does not run (vft_nj_options.intree).
     pseudo (float): `-pseudo W` - pseudocount distances in the minimum-evolution stages, 0 = off (vft_nj_options.pseudo_weight).
     ml_accuracy (int): `-mlacc N`; slow_nni: `-slownni`; nni_rounds / ml_nni_rounds (int > 0): `-nni N` / `-mlnni N` (0 rounds are
@@ -301,6 +314,8 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
     codes = np.ascontiguousarray(codes_all[unique_first])
     n, L = codes.shape
     ops = make_ops(n, L)
+    if approx_ml:
+        ops.set_approx_ml(True)
     me_nni, spr, ml_nni = zero_round_stages(me_nni, spr, ml_nni, nni_rounds, ml_nni_rounds)
     opt = _nj_options(fastest=fastest, use_tophits_2nd=second_level, scoredist=scoredist, mllen=mllen, me_nni=me_nni, ml_nni=ml_nni, spr=spr, gtr=gtr,
                       aa_model=aa_model, comm=comm, threads=threads, debug_flags=debug_flags, gamma=gamma, out_profile_parts=out_profile_parts, slow=slow,
@@ -571,6 +586,22 @@ class HipProfileOps:
             return
         a = [self.real(x) for x in (stat, statinv, eigenval, codefreq, eigeninv, eigeninvT)]
         self._chk(self.lib.vft_set_transition_matrix(self.ctx, *[_ptr(x) for x in a]))
+
+    def set_near_posteriors(self, near_p=None, near_freq=None):
+        """nearP / nearFreq [20, 20] of the transition matrix set last (aa_near_tables); set_transition_matrix clears them, so does None"""
+        if near_p is None and near_freq is None:
+            self._chk(self.lib.vft_set_near_posteriors(self.ctx, None, None))
+            return
+        a = [self.real(x) for x in (near_p, near_freq)]
+        assert a[0].shape == a[1].shape == (20, 20)
+        self._chk(self.lib.vft_set_near_posteriors(self.ctx, _ptr(a[0]), _ptr(a[1])))
+
+    def set_approx_ml(self, on=True):
+        """`-approxml`: posteriors under a 20-state matrix model take the near-constant approximation (needs set_near_posteriors)"""
+        self._chk(self.lib.vft_set_approx_ml(self.ctx, I32(1 if on else 0)))
+
+    def get_approx_ml(self):
+        return bool(self.lib.vft_get_approx_ml(self.ctx))
 
     def set_rates(self, rates, ratecat):
         rates = self.real(rates)

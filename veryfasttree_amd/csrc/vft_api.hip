@@ -119,6 +119,9 @@ struct vft_ctx {
     bool hasDm = false;
     void *tm[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     bool hasTm = false;
+    void *nearTab[2] = {nullptr, nullptr};   // vft_set_near_posteriors: nearP, nearFreq of the transition matrix set last
+    bool hasNear = false;
+    bool approxML = false;                // vft_set_approx_ml
     void *rates = nullptr;
     int32_t *ratecat = nullptr;
     int32_t nRates = 0;
@@ -309,6 +312,9 @@ static int ensure_scratch(vft_ctx *c, size_t bytes) {
     return own_regrow(c, &c->scratch, &c->scratchBytes, bytes + bytes / 2 + 4096);
 }
 
+// the posteriors take -approxml's near-constant branch: the switch, 20 states under a matrix model, and the tables
+static bool approx_on(const vft_ctx *c) { return c->approxML && c->hasTm && c->hasNear && c->d.nCodes == 20; }
+
 template <typename REAL>
 static Arena<REAL> arena(const vft_ctx *c) {
     Arena<REAL> A;
@@ -340,6 +346,9 @@ static Arena<REAL> arena(const vft_ctx *c) {
     A.tmCodeFreq = c->hasTm ? (const REAL *) c->tm[3] : nullptr;
     A.tmEigenInv = c->hasTm ? (const REAL *) c->tm[4] : nullptr;
     A.tmEigenInvT = c->hasTm ? (const REAL *) c->tm[5] : nullptr;
+    const bool rough = approx_on(c);
+    A.tmNearP = rough ? (const REAL *) c->nearTab[0] : nullptr;
+    A.tmNearFreq = rough ? (const REAL *) c->nearTab[1] : nullptr;
     A.rates = (const REAL *) c->rates;
     A.ratecat = c->ratecat;
     A.nRates = c->nRates;
@@ -669,6 +678,7 @@ static int context_init(vft_ctx *c, const vft_config *cfg) {
     OWNCHK(own_host(c, &c->hNOut, &c->dNOutM, (size_t) N * 4, (size_t) N * 4));
     for (int i = 0; i < 4; i++) OWNCHK(own_dev(c, &c->dm[i], (size_t) 21 * 20 * 8));
     for (int i = 0; i < 6; i++) OWNCHK(own_dev(c, &c->tm[i], (size_t) 21 * 20 * 8));
+    for (int i = 0; i < 2; i++) OWNCHK(own_dev(c, &c->nearTab[i], (size_t) 20 * 20 * 8));
     OWNCHK(own_dev(c, &c->rates, (size_t) VFT_MAXRATES * 8));
     OWNCHK(own_dev(c, &c->ratecat, (size_t) d.nPos * 4, 0));
     {
@@ -841,6 +851,7 @@ extern "C" int vft_set_distance_matrix(vft_ctx *c, const void *distances, const 
 extern "C" int vft_set_transition_matrix(vft_ctx *c, const void *stat, const void *statinv, const void *eigenval,
                                          const void *codefreq, const void *eigeninv, const void *eigeninvT) {
     if (!c) return VFT_ERR_INVALID;
+    c->hasNear = false;   // nearP / nearFreq belong to the matrix that is replaced here
     if (!stat) {
         if (c->d.nCodes != 4) return fail(c, VFT_ERR_INVALID, "Jukes-Cantor needs a nucleotide alphabet");
         c->hasTm = false;
@@ -867,6 +878,37 @@ extern "C" int vft_set_rates(vft_ctx *c, const void *rates, int32_t nRates, cons
     HIPCHK(c, hipMemcpyAsync(c->ratecat, rc.data(), rc.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->nRates = nRates;
+    return VFT_OK;
+}
+
+extern "C" int vft_set_near_posteriors(vft_ctx *c, const void *nearP, const void *nearFreq) {
+    if (!c) return VFT_ERR_INVALID;
+    if (!nearP && !nearFreq) {
+        c->hasNear = false;
+        return VFT_OK;
+    }
+    if (c->d.nCodes != 20) return fail(c, VFT_ERR_INVALID, "vft_set_near_posteriors: the near-constant posteriors are for 20 states");
+    if (!c->hasTm) return fail(c, VFT_ERR_STATE, "vft_set_near_posteriors: vft_set_transition_matrix first (the tables belong to a matrix)");
+    const void *src[2] = {nearP, nearFreq};
+    const size_t cnt[2] = {400, 400};
+    c->hasNear = false;
+    if (int r = upload_tables(c, c->nearTab, src, cnt, 2)) return r;
+    c->hasNear = true;
+    return VFT_OK;
+}
+
+extern "C" int vft_set_approx_ml(vft_ctx *c, int32_t on) {
+    if (!c) return VFT_ERR_INVALID;
+    c->approxML = on != 0;
+    return VFT_OK;
+}
+
+extern "C" int vft_get_approx_ml(vft_ctx *c) { return c && c->approxML ? 1 : 0; }
+
+// -approxml without its tables is an error, not the exact posterior under another name
+static int approx_ok(vft_ctx *c) {
+    if (c->approxML && c->d.nCodes == 20 && c->hasTm && !c->hasNear)
+        return fail(c, VFT_ERR_STATE, "approximate posteriors are on (vft_set_approx_ml) without nearP / nearFreq: vft_set_near_posteriors after vft_set_transition_matrix");
     return VFT_OK;
 }
 
@@ -3766,8 +3808,17 @@ static void launch_pair_loglk_any(vft_ctx *c, int64_t n, const int64_t *dA, cons
 // posteriors into dense ML rows (stash-free): one workgroup per node with quads, or the whole-column kernel
 static void launch_posterior_rows(vft_ctx *c, int64_t cnt, const int64_t *dOut, const int64_t *dA, const int64_t *dB, const double *dL1, const double *dL2) {
     if (quad_posterior_ok(c)) {
-        if (c->cfg.precision == 4) launch((k_posterior_quad<float>), dim3((unsigned) cnt), dim3(256), 0, c->stream, arena<float>(c), dOut, dA, dB, dL1, dL2, c->minLen, c->minRel);
-        else launch((k_posterior_quad<double>), dim3((unsigned) cnt), dim3(256), 0, c->stream, arena<double>(c), dOut, dA, dB, dL1, dL2, c->minLen, c->minRel);
+        const bool rough = approx_on(c);
+#define VFT_POSTQ_GO(REAL, APPROX) \
+    launch((k_posterior_quad<REAL, APPROX>), dim3((unsigned) cnt), dim3(256), 0, c->stream, arena<REAL>(c), dOut, dA, dB, dL1, dL2, c->minLen, c->minRel)
+        if (c->cfg.precision == 4) {
+            if (rough) VFT_POSTQ_GO(float, true);
+            else VFT_POSTQ_GO(float, false);
+        } else {
+            if (rough) VFT_POSTQ_GO(double, true);
+            else VFT_POSTQ_GO(double, false);
+        }
+#undef VFT_POSTQ_GO
         return;
     }
     VFT_DISPATCH(c, {
@@ -3807,6 +3858,7 @@ extern "C" int vft_posterior_profiles(vft_ctx *c, int64_t n, const int64_t *out,
     if (!c || n < 0 || !out || !a || !b || !len1 || !len2) return VFT_ERR_INVALID;
     if (n == 0) return VFT_OK;
     if (!c->hasTm && c->d.nCodes != 4) return fail(c, VFT_ERR_STATE, "amino-acid posteriors need vft_set_transition_matrix");
+    if (int r = approx_ok(c)) return r;
     for (int64_t k = 0; k < n; k++) {
         if (int r = internal_ok(c, out[k])) return r;
         if (a[k] < 0 || a[k] >= c->d.maxNodes || b[k] < 0 || b[k] >= c->d.maxNodes) return fail(c, VFT_ERR_INVALID, "vft_posterior_profiles: child %lld out of range", (long long) k);
@@ -3935,6 +3987,7 @@ extern "C" int vft_posterior_profiles_blen(vft_ctx *c, int64_t n, const int64_t 
     if (!c || n < 0 || !out || !a || !b || !lenIdxA || !lenIdxB) return VFT_ERR_INVALID;
     if (n == 0) return VFT_OK;
     if (!c->hasTm && c->d.nCodes != 4) return fail(c, VFT_ERR_STATE, "amino-acid posteriors need vft_set_transition_matrix");
+    if (int r = approx_ok(c)) return r;
     for (int64_t k = 0; k < n; k++) {
         if (int r = internal_ok(c, out[k])) return r;
         if (lenIdxA[k] < 0 || lenIdxA[k] >= c->d.maxNodes || lenIdxB[k] < 0 || lenIdxB[k] >= c->d.maxNodes || a[k] < 0 ||
@@ -3976,6 +4029,7 @@ static int posterior_chains(vft_ctx *c, int32_t nChains, const int32_t *chainOff
                             const int64_t *b, const int64_t *lenIdxA, const int64_t *lenIdxB, const char *who) {
     if (n == 0) return VFT_OK;
     if (!c->hasTm && c->d.nCodes != 4) return fail(c, VFT_ERR_STATE, "amino-acid posteriors need vft_set_transition_matrix");
+    if (int r = approx_ok(c)) return r;
     for (int32_t k = 0; k < n; k++) {
         if (int r = internal_ok(c, out[k])) return r;
         if (a[k] < 0 || a[k] >= c->d.maxNodes || b[k] < 0 || b[k] >= c->d.maxNodes || lenIdxA[k] < 0 || lenIdxA[k] >= c->d.maxNodes ||
@@ -4054,19 +4108,24 @@ static int ml_optimize_launch(vft_ctx *c, int64_t n, int cpt, bool quad, const i
                (REAL *) c->blen, c->minLen, c->minRel, ftol, atol, c->mlEvals, c->mlLongWs, stride);
         return VFT_OK;
     }
-#define VFT_MLOPT_GO(CPT, QUAD)                                                                                         \
-    launch((k_ml_node_lengths<REAL, NC, CPT, QUAD>), dim3((unsigned) n), dim3(MlLineWG<NC, QUAD>::value), 0, c->stream, arena<REAL>(c), \
+#define VFT_MLOPT_GO(CPT, QUAD, APPROX)                                                                                 \
+    launch((k_ml_node_lengths<REAL, NC, CPT, QUAD, APPROX>), dim3((unsigned) n), dim3(MlLineWG<NC, QUAD>::value), 0, c->stream, arena<REAL>(c), \
            dIds, dLi, dRec, (REAL *) c->blen, c->minLen, c->minRel, ftol, atol, c->mlEvals)
     if constexpr (NC == 20) {
-        if (quad && cpt == 2) VFT_MLOPT_GO(2, true);
-        else if (quad && cpt == 5) VFT_MLOPT_GO(5, true);
-        else if (quad && cpt == 8) VFT_MLOPT_GO(8, true);
-        else if (!quad && cpt == 4) VFT_MLOPT_GO(4, false);
+        const bool rough = approx_on(c);   // the instances with the near-constant branch (VFT_ML_APPROX_INSTANCES)
+        if (quad && cpt == 2 && rough) VFT_MLOPT_GO(2, true, true);
+        else if (quad && cpt == 5 && rough) VFT_MLOPT_GO(5, true, true);
+        else if (quad && cpt == 8 && rough) VFT_MLOPT_GO(8, true, true);
+        else if (!quad && cpt == 4 && rough) VFT_MLOPT_GO(4, false, true);
+        else if (quad && cpt == 2) VFT_MLOPT_GO(2, true, false);
+        else if (quad && cpt == 5) VFT_MLOPT_GO(5, true, false);
+        else if (quad && cpt == 8) VFT_MLOPT_GO(8, true, false);
+        else if (!quad && cpt == 4) VFT_MLOPT_GO(4, false, false);
         else return fail(c, VFT_ERR_INVALID, "vft_ml_optimize_splits: alignment too long for the in-kernel optimiser");
     } else {
-        if (cpt == 1) VFT_MLOPT_GO(1, false);
-        else if (cpt == 4) VFT_MLOPT_GO(4, false);
-        else if (cpt == 8) VFT_MLOPT_GO(8, false);
+        if (cpt == 1) VFT_MLOPT_GO(1, false, false);
+        else if (cpt == 4) VFT_MLOPT_GO(4, false, false);
+        else if (cpt == 8) VFT_MLOPT_GO(8, false, false);
         else return fail(c, VFT_ERR_INVALID, "vft_ml_optimize_splits: alignment too long for the in-kernel optimiser");
     }
 #undef VFT_MLOPT_GO
@@ -4082,6 +4141,7 @@ extern "C" int vft_ml_optimize_splits(vft_ctx *c, int64_t n, const int64_t *ids,
     if (!c || n < 0 || !ids || !lenIdx || !recompute) return VFT_ERR_INVALID;
     if (n == 0) return VFT_OK;
     if (!c->hasTm && c->d.nCodes != 4) return fail(c, VFT_ERR_STATE, "amino-acid likelihoods need vft_set_transition_matrix");
+    if (int r = approx_ok(c)) return r;
     const bool rec = recompute[0] >= 0;
     for (int64_t k = 0; k < n; k++) {
         if ((recompute[k] >= 0) != rec) return fail(c, VFT_ERR_INVALID, "vft_ml_optimize_splits: mixed recompute flags");
@@ -4126,20 +4186,25 @@ static int ml_quartet_launch(vft_ctx *c, int64_t n, int cpt, bool quad, const in
                c->mlLongWs, stride);
         return VFT_OK;
     }
-#define VFT_MLQ_GO(CPT, QUAD)                                                                                           \
-    launch((k_ml_quartet<REAL, NC, CPT, QUAD>), dim3((unsigned) n, mode == 2 ? 3u : 1u), dim3(MlLineWG<NC, QUAD>::value), 0, c->stream, \
+#define VFT_MLQ_GO(CPT, QUAD, APPROX)                                                                                   \
+    launch((k_ml_quartet<REAL, NC, CPT, QUAD, APPROX>), dim3((unsigned) n, mode == 2 ? 3u : 1u), dim3(MlLineWG<NC, QUAD>::value), 0, c->stream, \
            arena<REAL>(c), dIds, dLi, (REAL *) c->blen, c->minLen, c->minRel, ftol, atol, closeLimit, mlAccuracy, mode,  \
            dLoglk, dSite, dLen, dNni, dState, c->mlEvals)
     if constexpr (NC == 20) {
-        if (quad && cpt == 2) VFT_MLQ_GO(2, true);
-        else if (quad && cpt == 5) VFT_MLQ_GO(5, true);
-        else if (quad && cpt == 8) VFT_MLQ_GO(8, true);
-        else if (!quad && cpt == 4) VFT_MLQ_GO(4, false);
+        const bool rough = approx_on(c);   // the instances with the near-constant branch (VFT_ML_APPROX_INSTANCES)
+        if (quad && cpt == 2 && rough) VFT_MLQ_GO(2, true, true);
+        else if (quad && cpt == 5 && rough) VFT_MLQ_GO(5, true, true);
+        else if (quad && cpt == 8 && rough) VFT_MLQ_GO(8, true, true);
+        else if (!quad && cpt == 4 && rough) VFT_MLQ_GO(4, false, true);
+        else if (quad && cpt == 2) VFT_MLQ_GO(2, true, false);
+        else if (quad && cpt == 5) VFT_MLQ_GO(5, true, false);
+        else if (quad && cpt == 8) VFT_MLQ_GO(8, true, false);
+        else if (!quad && cpt == 4) VFT_MLQ_GO(4, false, false);
         else return fail(c, VFT_ERR_INVALID, "alignment too long for the in-kernel quartet optimiser");
     } else {
-        if (cpt == 1) VFT_MLQ_GO(1, false);
-        else if (cpt == 4) VFT_MLQ_GO(4, false);
-        else if (cpt == 8) VFT_MLQ_GO(8, false);   // nucleotides up to 2048 columns (16S-length alignments)
+        if (cpt == 1) VFT_MLQ_GO(1, false, false);
+        else if (cpt == 4) VFT_MLQ_GO(4, false, false);
+        else if (cpt == 8) VFT_MLQ_GO(8, false, false);   // nucleotides up to 2048 columns (16S-length alignments)
         else return fail(c, VFT_ERR_INVALID, "alignment too long for the in-kernel quartet optimiser");
     }
 #undef VFT_MLQ_GO
@@ -4162,6 +4227,7 @@ static int ml_quartet_nni(vft_ctx *c, int64_t n, const int64_t *ids, const int64
                           double closeLimit, int32_t mlAccuracy, int32_t flags, vft_quartet_nni *results) {
     if (!c || n < 1 || !ids || !lenIdx || !results) return VFT_ERR_INVALID;
     if (!c->hasTm && c->d.nCodes != 4) return fail(c, VFT_ERR_STATE, "amino-acid likelihoods need vft_set_transition_matrix");
+    if (int r = approx_ok(c)) return r;
     if (int r = quartet_args_ok(c, n, ids, lenIdx, "vft_ml_quartet_nni")) return r;
     if (int r = ensure_blen(c)) return r;
     if (!c->mlEvals) OWNCHK(own_dev(c, &c->mlEvals, sizeof(unsigned int), 0, ON_STREAM));
@@ -4227,6 +4293,7 @@ extern "C" int vft_ml_split_tests(vft_ctx *c, int64_t n, const int64_t *ids, con
     if (!c || n < 0 || !ids || !lenIdx || !loglk || (nBoot > 0 && (!col || !support))) return VFT_ERR_INVALID;
     if (n == 0) return VFT_OK;
     if (!c->hasTm && c->d.nCodes != 4) return fail(c, VFT_ERR_STATE, "amino-acid likelihoods need vft_set_transition_matrix");
+    if (int r = approx_ok(c)) return r;
     if (int r = quartet_args_ok(c, n, ids, lenIdx, "vft_ml_split_tests")) return r;
     if (int r = ensure_blen(c)) return r;
     if (!c->mlEvals) OWNCHK(own_dev(c, &c->mlEvals, sizeof(unsigned int), 0, ON_STREAM));

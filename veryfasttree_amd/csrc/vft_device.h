@@ -28,6 +28,9 @@ struct Arena {
     const REAL *dmDist, *dmCodeFreq, *dmEigenval, *dmEigentot;
     // transition matrix (NULL for Jukes-Cantor): codefreq has nCodes+1 rows
     const REAL *tmStat, *tmStatInv, *tmEigenval, *tmCodeFreq, *tmEigenInv, *tmEigenInvT;
+    // -approxml (vft_set_approx_ml + vft_set_near_posteriors): nearP / nearFreq [20][20] of the transition matrix, NULL = every
+    // posterior takes the exact rotation (always NULL for 4 states)
+    const REAL *tmNearP, *tmNearFreq;
     const REAL *rates;
     const int32_t *ratecat;
     int32_t nRates;

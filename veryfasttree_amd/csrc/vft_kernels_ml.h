@@ -705,10 +705,15 @@ __global__ __launch_bounds__(VFT_ML_WG) void k_pair_loglk(Arena<REAL> A, const i
     }
 }
 
+// -approxml (Constants.h:46-48): try the near-constant posterior when one state holds this much, keep it while rough / true >= ratio
+#define VFT_APPROX_MINF 0.95
+#define VFT_APPROX_MINRATIO (2 / 3.0)
+
 // One column of posteriorProfile (NJ.tcc:2185-2260 Jukes-Cantor incl. the "simple profile" shortcuts, :2262-2434 matrix
-// models, exact ML): weight, code and - when code == NOCODE and weight > 0 - the frequency vector of the parent.
-// PS/PD resp. e1/e2 belong to the column's rate category and the two branch lengths.
-template <typename REAL, int NC>
+// models): weight, code and - when code == NOCODE and weight > 0 - the frequency vector of the parent.
+// PS/PD resp. e1/e2 belong to the column's rate category and the two branch lengths.  Exact ML unless the arena carries the
+// near-constant tables (Arena::tmNearP, 20 states only): then a column with a dominant state skips the rotation (:2390-2421).
+template <typename REAL, int NC, bool APPROX = true>
 __device__ __forceinline__ void vft_posterior_col(const Arena<REAL> &A, const Col<REAL, NC> &c1, const Col<REAL, NC> &c2,
                                                   bool jc, double PS1, double PD1, double PS2, double PD2,
                                                   const REAL *e1, const REAL *e2, REAL &wo, int &co, REAL *f) {
@@ -835,11 +840,42 @@ __device__ __forceinline__ void vft_posterior_col(const Arena<REAL> &A, const Co
                 const REAL invr = (REAL) (1.0 / tot);
 #pragma unroll
                 for (int j = 0; j < NC; j++) fPost[j] = fPost[j] * invr;
-                for (int j = 0; j < NC; j++) {
-                    REAL ei[NC];
+                // -approxml (NJ.tcc:2390-2421): a dominant state ch and the rest close to nearP[ch] -> no rotation
+                int ch = -1;
+                double w = 0;
+                if (APPROX && A.tmNearP != nullptr) {   // (APPROX: the line-search kernels keep the branch out of their exact instances)
+                    REAL fCh = 0;
 #pragma unroll
-                    for (int q = 0; q < NC; q++) ei[q] = A.tmEigenInv[j * NC + q];
-                    f[j] = vft_red4_mul<REAL, NC>(fPost, ei);
+                    for (int j = NC - 1; j >= 0; j--)
+                        if ((double) fPost[j] >= VFT_APPROX_MINF) {   // ends at the first such j in index order
+                            ch = j;
+                            fCh = fPost[j];
+                        }
+                    if (ch >= 0) {
+                        const REAL *np = A.tmNearP + ch * NC;
+                        const REAL pcc = np[ch];
+                        w = (double) (fCh - pcc) / (1.0 - (double) pcc);   // numeric_t - numeric_t is a numeric_t in the reference
+                        bool giveUp = false;   // (the reference stops at the first failure: no value depends on that)
+#pragma unroll
+                        for (int j = 0; j < NC; j++) {
+                            const double fRough = (1.0 - w) * (double) np[j];
+                            if (j != ch && fRough < (double) fPost[j] * VFT_APPROX_MINRATIO) giveUp = true;
+                        }
+                        if (giveUp) ch = -1;
+                    }
+                }
+                if (ch >= 0) {
+                    const double wInvStat = w * (double) A.tmStatInv[ch];
+                    const REAL *cf = A.tmCodeFreq + ch * NC, *nf = A.tmNearFreq + ch * NC;
+#pragma unroll
+                    for (int j = 0; j < NC; j++) f[j] = (REAL) (wInvStat * (double) cf[j] + (1.0 - w) * (double) nf[j]);
+                } else {
+                    for (int j = 0; j < NC; j++) {
+                        REAL ei[NC];
+#pragma unroll
+                        for (int q = 0; q < NC; q++) ei[q] = A.tmEigenInv[j * NC + q];
+                        f[j] = vft_red4_mul<REAL, NC>(fPost, ei);
+                    }
                 }
             }
         }
@@ -961,6 +997,26 @@ __device__ __forceinline__ double vft_quad_perm(double x) {
     const int lo = __builtin_amdgcn_update_dpp(0, (int) (b & 0xFFFFFFFFll), CTRL, 0xF, 0xF, false);
     const int hi = __builtin_amdgcn_update_dpp(0, (int) (b >> 32), CTRL, 0xF, 0xF, false);
     return __longlong_as_double(((long long) hi << 32) | (long long) (unsigned int) lo);
+}
+template <int CTRL>
+__device__ __forceinline__ int vft_quad_perm(int x) {
+    return __builtin_amdgcn_update_dpp(0, x, CTRL, 0xF, 0xF, false);
+}
+// the least of the four lanes' values / whether any lane's flag is set, on all four lanes
+__device__ __forceinline__ int vft_quad_min(int x) {
+    const int o = vft_quad_perm<0xB1>(x), a = o < x ? o : x;
+    const int p = vft_quad_perm<0x4E>(a);
+    return p < a ? p : a;
+}
+__device__ __forceinline__ bool vft_quad_any(bool x) {
+    const int a = (int) x | vft_quad_perm<0xB1>((int) x);
+    return (a | vft_quad_perm<0x4E>(a)) != 0;
+}
+// lane `src`'s x on all four lanes (src: the same on all four)
+template <typename REAL>
+__device__ __forceinline__ REAL vft_quad_from(REAL x, int src) {
+    const REAL x0 = vft_quad_perm<0x00>(x), x1 = vft_quad_perm<0x55>(x), x2 = vft_quad_perm<0xAA>(x), x3 = vft_quad_perm<0xFF>(x);
+    return src == 0 ? x0 : src == 1 ? x1 : src == 2 ? x2 : x3;
 }
 // accumulator l on lane l -> (s0 + s1) + (s2 + s3) on all four lanes (additions commute: every lane forms the same two sums)
 template <typename REAL>
@@ -1097,9 +1153,11 @@ __device__ __forceinline__ bool vft_quad_pair_lk_col(const MlQuadTables<REAL> *Q
     return true;
 }
 
-// vft_posterior_col under a matrix model with 20 states (NJ.tcc:2267-2447), lane l's states of the result
-template <typename REAL>
-__device__ __forceinline__ void vft_quad_posterior_col(const MlQuadTables<REAL> *Q, const Col<REAL, VFT_QS> &c1, const Col<REAL, VFT_QS> &c2,
+// vft_posterior_col under a matrix model with 20 states (NJ.tcc:2267-2447), lane l's states of the result.  nearP / nearFreq: the arena's
+// tmNearP / tmNearFreq (NULL: exact) - read where they lie, a row per rough column: the LDS tables, and with them the exact path, stay as they were
+template <typename REAL, bool APPROX = true>
+__device__ __forceinline__ void vft_quad_posterior_col(const MlQuadTables<REAL> *Q, const REAL *nearP, const REAL *nearFreq,
+                                                       const Col<REAL, VFT_QS> &c1, const Col<REAL, VFT_QS> &c2,
                                                        const REAL *e1, const REAL *e2, int l, Col<REAL, VFT_QS> &o) {
     o.w = (REAL) 1.0;
     o.code = VFT_NOCODE_;
@@ -1165,6 +1223,39 @@ __device__ __forceinline__ void vft_quad_posterior_col(const MlQuadTables<REAL> 
     const REAL invr = (REAL) (1.0 / tot);
 #pragma unroll
     for (int i = 0; i < VFT_QS; i++) fPost[i] = fPost[i] * invr;
+    o.vec = true;   // code == NOCODE, w == 1
+    // -approxml (NJ.tcc:2390-2421, vft_posterior_col): the dominant state ch, the give-up test and therefore the branch are
+    // decided for the QUAD - every exchange below, and those of the rotation, runs with all four lanes of a quad or none.
+    // State order is not lane order (j = l + 4 i): the first j at or above the threshold is the least of the lanes' own firsts.
+    if (APPROX && nearP != nullptr) {
+        int mine = 20;
+#pragma unroll
+        for (int i = VFT_QS - 1; i >= 0; i--)
+            if ((double) fPost[i] >= VFT_APPROX_MINF) mine = l + 4 * i;
+        const int first = vft_quad_min(mine);
+        const int ch = first < 20 ? first : 0;   // (no such state: row 0 is read and dropped)
+        REAL own = fPost[0];
+#pragma unroll
+        for (int i = 1; i < VFT_QS; i++) own = i == (ch >> 2) ? fPost[i] : own;
+        const REAL fCh = vft_quad_from<REAL>(own, ch & 3);
+        const REAL *np = nearP + ch * 20;
+        const REAL pcc = np[ch];
+        const double w = (double) (fCh - pcc) / (1.0 - (double) pcc);
+        bool giveUp = false;
+#pragma unroll
+        for (int i = 0; i < VFT_QS; i++) {
+            const int j = l + 4 * i;
+            const double fRough = (1.0 - w) * (double) np[j];
+            if (j != ch && fRough < (double) fPost[i] * VFT_APPROX_MINRATIO) giveUp = true;
+        }
+        if (first < 20 && !vft_quad_any(giveUp)) {
+            const double wInvStat = w * (double) Q->statInv[ch];
+            const REAL *cf = Q->codeFreq + ch * 20, *nf = nearFreq + ch * 20;
+#pragma unroll
+            for (int i = 0; i < VFT_QS; i++) o.f[i] = (REAL) (wInvStat * (double) cf[l + 4 * i] + (1.0 - w) * (double) nf[l + 4 * i]);
+            return;
+        }
+    }
 #pragma unroll
     for (int i = 0; i < VFT_QS; i++) {
         g1[4 * i] = vft_quad_perm<0x00>(fPost[i]);
@@ -1189,7 +1280,6 @@ __device__ __forceinline__ void vft_quad_posterior_col(const MlQuadTables<REAL> 
 #pragma unroll
         for (int q = 0; q < VFT_QS; q++) o.f[q] = q == jq ? v : o.f[q];
     }
-    o.vec = true;   // code == NOCODE, w == 1
 }
 
 // element idx of a small array that must stay in registers (a runtime index would send it to scratch memory)
@@ -1257,7 +1347,9 @@ __global__ __launch_bounds__(256) void k_pair_loglk_quad(Arena<REAL> A, const in
     if (threadIdx.x == 0) loglkOut[k] = tot;
 }
 
-template <typename REAL>
+// APPROX: the instance that can take the near-constant branch (Arena::tmNearP).  A template flag, not the arena's pointer alone: with the
+// branch compiled in, the double instance needs 229 VGPRs instead of 161 - two waves per SIMD instead of three for every exact run.
+template <typename REAL, bool APPROX>
 __global__ __launch_bounds__(256) void k_posterior_quad(Arena<REAL> A, const int64_t *outN, const int64_t *aN, const int64_t *bN,
                                                         const double *len1A, const double *len2A, double minLen, double minRel) {
     constexpr int CW = 64;
@@ -1281,7 +1373,7 @@ __global__ __launch_bounds__(256) void k_posterior_quad(Arena<REAL> A, const int
         vft_quad_load_col_ml<REAL>(A, a, p, ql, c1);
         vft_quad_load_col_ml<REAL>(A, b, p, ql, c2);
         const int r = A.ratecat[p];
-        vft_quad_posterior_col<REAL>(&quadTab, c1, c2, ee1 + r * 20, ee2 + r * 20, ql, o);
+        vft_quad_posterior_col<REAL, APPROX>(&quadTab, A.tmNearP, A.tmNearFreq, c1, c2, ee1 + r * 20, ee2 + r * 20, ql, o);
         vft_quad_store_col_ml<REAL>(A, out, p, ql, o.w, o.code, o.f);
     }
     if (threadIdx.x == 0) A.mlIs[out - A.d.nSeqs] = 1;
@@ -1428,7 +1520,7 @@ __device__ __forceinline__ double vft_min_branch_length(EVAL &&eval, double xmin
     return x;
 }
 
-template <typename REAL, int NC, int CPT, bool QUAD>
+template <typename REAL, int NC, int CPT, bool QUAD, bool APPROX = false>
 __global__ __launch_bounds__((MlLineWG<NC, QUAD>::value)) void k_ml_node_lengths(Arena<REAL> A, const int64_t *ids, const int64_t *lenIdx,
                                                                   const int64_t *recN, REAL *blen, double minLen,
                                                                   double minRel, double ftol, double atol,
@@ -1483,9 +1575,9 @@ __global__ __launch_bounds__((MlLineWG<NC, QUAD>::value)) void k_ml_node_lengths
     // posteriorProfile of one column from the tables in ee1 / ee2 (pS1.. under Jukes-Cantor)
     auto post = [&](const ColT &c1, const ColT &c2, int r, ColT &o) __attribute__((always_inline)) {
         if constexpr (QUAD) {
-            vft_quad_posterior_col<REAL>(&quadTab, c1, c2, ee1 + r * NC, ee2 + r * NC, ql, o);
+            vft_quad_posterior_col<REAL, APPROX>(&quadTab, A.tmNearP, A.tmNearFreq, c1, c2, ee1 + r * NC, ee2 + r * NC, ql, o);
         } else {
-            vft_posterior_col<REAL, NC>(A, c1, c2, jc, pS1[r], pD1[r], pS2[r], pD2[r], ee1 + r * NC, ee2 + r * NC, o.w, o.code, o.f);
+            vft_posterior_col<REAL, NC, APPROX>(A, c1, c2, jc, pS1[r], pD1[r], pS2[r], pD2[r], ee1 + r * NC, ee2 + r * NC, o.w, o.code, o.f);
             o.vec = o.code == VFT_NOCODE_ && o.w > (REAL) 0;
         }
     };
@@ -1619,7 +1711,7 @@ struct QuartetNNIState {
     int32_t consider1, consider2, done, star;
 };
 
-template <typename REAL, int NC, int CPT, bool QUAD>
+template <typename REAL, int NC, int CPT, bool QUAD, bool APPROX = false>
 __global__ __launch_bounds__((MlLineWG<NC, QUAD>::value)) void k_ml_quartet(Arena<REAL> A, const int64_t *ids, const int64_t *lenIdx, REAL *blen,
                                                              double minLen, double minRel, double ftol, double atol,
                                                              double closeLimit, int mlAccuracy, int mode, double *loglkOut,
@@ -1667,10 +1759,10 @@ __global__ __launch_bounds__((MlLineWG<NC, QUAD>::value)) void k_ml_quartet(Aren
     auto post = [&](const ColT &c1, const ColT &c2, int s1, int s2, int r, ColT &o) __attribute__((always_inline)) {
         if (r < 0) return;
         if constexpr (QUAD) {
-            vft_quad_posterior_col<REAL>(&quadTab, c1, c2, ee[s1] + r * NC, ee[s2] + r * NC, ql, o);
+            vft_quad_posterior_col<REAL, APPROX>(&quadTab, A.tmNearP, A.tmNearFreq, c1, c2, ee[s1] + r * NC, ee[s2] + r * NC, ql, o);
         } else {
-            vft_posterior_col<REAL, NC>(A, c1, c2, jc, pS[s1][r], pD[s1][r], pS[s2][r], pD[s2][r], ee[s1] + r * NC, ee[s2] + r * NC,
-                                        o.w, o.code, o.f);
+            vft_posterior_col<REAL, NC, APPROX>(A, c1, c2, jc, pS[s1][r], pD[s1][r], pS[s2][r], pD[s2][r], ee[s1] + r * NC, ee[s2] + r * NC,
+                                                o.w, o.code, o.f);
             o.vec = o.code == VFT_NOCODE_ && o.w > (REAL) 0;
         }
     };
@@ -2154,7 +2246,23 @@ static __global__ __launch_bounds__(256) void k_sh_support(const double *siteLog
     VFT_ML_QUARTET_INSTANCE(PFX, double, 20, 5, true)       \
     VFT_ML_QUARTET_INSTANCE(PFX, double, 20, 8, true)           \
     VFT_ML_QUARTET_INSTANCE(PFX, double, 20, 4, false)
+// -approxml: the 20-state instances once more with the near-constant branch of the posteriors compiled in (APPROX; the exact
+// instances above keep their registers: with the branch behind the arena's pointer alone k_ml_quartet<double, 20, 5, true> spilled
+// 743 VGPRs instead of 576).  Units of their own, vft_ml_kernels_approx32 / 64.hip.
+#define VFT_ML_APPROX_INSTANCE(PFX, REAL, CPT, QUAD)                                                                        \
+    PFX template __global__ void k_ml_node_lengths<REAL, 20, CPT, QUAD, true>(Arena<REAL>, const int64_t *, const int64_t *, const int64_t *, \
+                                                                             REAL *, double, double, double, double, unsigned int *);        \
+    PFX template __global__ void k_ml_quartet<REAL, 20, CPT, QUAD, true>(Arena<REAL>, const int64_t *, const int64_t *, REAL *, double, double, \
+                                                                        double, double, double, int, int, double *, double *, double *,  \
+                                                                        QuartetNNIResult *, QuartetNNIState *, unsigned int *);
+#define VFT_ML_APPROX_INSTANCES(PFX, REAL)      \
+    VFT_ML_APPROX_INSTANCE(PFX, REAL, 2, true)  \
+    VFT_ML_APPROX_INSTANCE(PFX, REAL, 5, true)  \
+    VFT_ML_APPROX_INSTANCE(PFX, REAL, 8, true)  \
+    VFT_ML_APPROX_INSTANCE(PFX, REAL, 4, false)
 #define VFT_ML_HEAVY_INSTANCES(PFX)        \
     VFT_ML_NODE_LENGTHS_INSTANCES(PFX)     \
     VFT_ML_QUARTET_INSTANCES_F32(PFX)      \
-    VFT_ML_QUARTET_INSTANCES_F64(PFX)
+    VFT_ML_QUARTET_INSTANCES_F64(PFX)      \
+    VFT_ML_APPROX_INSTANCES(PFX, float)    \
+    VFT_ML_APPROX_INSTANCES(PFX, double)

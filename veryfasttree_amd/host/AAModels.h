@@ -52,6 +52,44 @@ namespace veryfasttree {
         createTransitionTables<REAL, 20>(matrix, stat, t);
     }
 
+    /* what vft_set_near_posteriors takes: numeric_t values held in double */
+    struct NearTables20 {
+        double nearP[20][20], nearFreq[20][20];
+    };
+
+    /* The tail of createTransitionMatrix (TransitionMatrix.tcc:227-279), `-approxml`'s near-constant posteriors: P(t = approxMLnearT)
+       from the STORED (numeric_t) tables in double, nearP[i][j] ~ stat[j] * P(j -> i | t)^2 normalised, nearFreq[i] = nearP[i] / stat
+       rotated by codeFreq - statement for statement in the reference's order, with the host's exp (the rotation's inner product
+       reads codeFreq[i][j] for every k, as the reference's does) */
+    template<typename REAL>
+    inline void nearPosteriorTables(const TransitionTables20 &t, NearTables20 &n) {
+        const double nearT = 0.2;   /* Constants::approxMLnearT */
+        double expvalues[20], LVinv[20][20], transt[20][20];
+        for (int i = 0; i < 20; i++) expvalues[i] = std::exp(nearT * t.eigenval[i]);
+        for (int i = 0; i < 20; i++)
+            for (int j = 0; j < 20; j++) LVinv[i][j] = t.eigeninv[i][j] * expvalues[i];
+        for (int i = 0; i < 20; i++)
+            for (int j = 0; j < 20; j++) {
+                transt[i][j] = 0;
+                for (int k = 0; k < 20; k++) transt[i][j] += t.codeFreq[i][k] * LVinv[k][j];
+            }
+        for (int i = 0; i < 20; i++) {
+            double p[20], tot = 0;
+            for (int j = 0; j < 20; j++) {
+                p[j] = t.stat[j] * transt[i][j] * transt[i][j];
+                tot += p[j];
+            }
+            for (int j = 0; j < 20; j++) p[j] *= 1.0 / tot;
+            for (int j = 0; j < 20; j++) n.nearP[i][j] = (double) (REAL) p[j];
+            for (int j = 0; j < 20; j++) p[j] /= t.stat[j];
+            for (int j = 0; j < 20; j++) {
+                double rot = 0;
+                for (int k = 0; k < 20; k++) rot += p[k] * t.codeFreq[i][j];
+                n.nearFreq[i][j] = (double) (REAL) rot;
+            }
+        }
+    }
+
     /* matrixBLOSUM45 + setupDistanceMatrix: the literals are narrowed to numeric_t where the reference's static
        initialiser narrows them; eigentot is summed in numeric_t (DistanceMatrix.tcc:127-133), codeFreq is the
        transpose of eigeninv (:135-140) */

@@ -195,6 +195,14 @@ namespace veryfasttree {
             chk(vft_set_transition_matrix(ctx, stat, statinv, eigenval, codeFreq, eigeninv, eigeninvT));
         }
 
+        /* TransitionMatrix::nearP / nearFreq of the matrix set last ([20][20] each); setTransitionMatrix clears them */
+        void setNearPosteriors(const numeric_t *nearP, const numeric_t *nearFreq) {
+            chk(vft_set_near_posteriors(ctx, nearP, nearFreq));
+        }
+
+        /* !options.exactML (`-approxml`): posteriorProfile takes the near-constant approximation where it holds (NJ.tcc:2390-2421) */
+        void setApproxML(bool on) { chk(vft_set_approx_ml(ctx, on ? 1 : 0)); }
+
         void setRates(const numeric_t *rates, int32_t nRates, const int64_t *ratecat) {
             chk(vft_set_rates(ctx, rates, nRates, ratecat));
         }

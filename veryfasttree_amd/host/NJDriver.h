@@ -1207,6 +1207,17 @@ namespace veryfasttree {
             for (int i = 0; i < 21; i++)
                 for (int j = 0; j < 20; j++) cf[20 * i + j] = (REAL) t.codeFreq[i][j];
             chkT("vft_set_transition_matrix", [&]() { return vft_set_transition_matrix(ctx, stat, statinv, eval, cf, ei, eiT); });
+            /* options.exactML: the near-constant posteriors always travel with the model (2 x 400 values); the context's switch
+               (vft_set_approx_ml, the caller's `-approxml`) alone decides whether a posterior reads them */
+            NearTables20 nearT;
+            nearPosteriorTables<REAL>(t, nearT);
+            REAL nearP[400], nearFreq[400];
+            for (int i = 0; i < 20; i++)
+                for (int j = 0; j < 20; j++) {
+                    nearP[20 * i + j] = (REAL) nearT.nearP[i][j];
+                    nearFreq[20 * i + j] = (REAL) nearT.nearFreq[i][j];
+                }
+            chkT("vft_set_near_posteriors", [&]() { return vft_set_near_posteriors(ctx, nearP, nearFreq); });
         }
 
         /* optional per-entry-point wall-clock accounting (VFT_NJ_PROFILE=1) */

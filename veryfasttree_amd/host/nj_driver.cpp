@@ -577,6 +577,29 @@ extern "C" int vft_aa_model_tables(int32_t model, int32_t precision, double *sta
     }
 }
 
+extern "C" int vft_aa_near_tables(int32_t model, int32_t precision, double *nearP, double *nearFreq) {
+    if (!nearP || !nearFreq || (precision != 4 && precision != 8)) return VFT_ERR_INVALID;
+    try {
+        veryfasttree::TransitionTables20 t;
+        veryfasttree::NearTables20 n;
+        if (precision == 8) {
+            veryfasttree::createAAModel<double>(model, t);
+            veryfasttree::nearPosteriorTables<double>(t, n);
+        } else {
+            veryfasttree::createAAModel<float>(model, t);
+            veryfasttree::nearPosteriorTables<float>(t, n);
+        }
+        for (int i = 0; i < 20; i++)
+            for (int j = 0; j < 20; j++) {
+                nearP[20 * i + j] = n.nearP[i][j];
+                nearFreq[20 * i + j] = n.nearFreq[i][j];
+            }
+        return VFT_OK;
+    } catch (const std::exception &) {
+        return VFT_ERR_INVALID;
+    }
+}
+
 static void distanceTablesOut(const veryfasttree::DistanceTables20 &d, double *distances, double *codefreq, double *eigenval,
                               double *eigentot) {
     for (int i = 0; i < 20; i++) {

@@ -15,7 +15,7 @@ n_bootstrap: `-boot N`, 0 with -nosupport, else 1000; kwargs: the keyword argume
 other: what nj_newick has no keyword for and the caller has to act on - makematrix, rawdist, notop (True), seed (int)."""
 
 SWITCHES = ("-nt", "-double-precision", "-lg", "-wag", "-gtr", "-gamma", "-noml", "-nome", "-mllen", "-nocat", "-nosupport", "-slow",
-            "-fastest", "-2nd", "-no2nd", "-notop", "-slownni", "-makematrix", "-rawdist")
+            "-fastest", "-2nd", "-no2nd", "-notop", "-slownni", "-makematrix", "-rawdist", "-approxml", "-mlapprox")
 # flag: (least, most, what the message asks for beyond "a whole number")
 COUNTS = {"-spr": (0, None, ">= 0"), "-mlacc": (1, None, ">= 1"), "-nni": (0, None, ">= 0"), "-mlnni": (0, None, ">= 0"),
           "-sprlength": (1, 64, "from 1 to 64 (the SPR chain buffers hold 64 steps)"), "-cat": (1, None, ">= 1"),
@@ -126,6 +126,12 @@ def from_reference_flags(flags, threads=None, intree_text=None):
         kw.update({key: True for key in ("gtr", "gamma") if "-" + key in f})
     if "-slownni" in f:
         kw["slow_nni"] = True
+    # -approxml / -mlapprox (main.cpp:216, one option with two names): posteriorProfile reads it for 20 states alone, and only an ML
+    # stage computes posteriors - under -nt or -noml the reference accepts it and nothing changes, so it translates to nothing
+    if "-approxml" in f and "-mlapprox" in f:
+        raise ValueError("-mlapprox is -approxml under its other name: the option is given twice")
+    if ("-approxml" in f or "-mlapprox" in f) and not nt and ("-mllen" in f or ml_nni):
+        kw["approx_ml"] = True
     kw.update({key: f[flag] for flag, key in THOROUGH.items() if f.get(flag)})   # (a count of 0 has become the switches above)
     n_bootstrap = 0 if "-nosupport" in f else f.get("-boot", 1000)
     other = {key: f["-" + key] for key in ("makematrix", "rawdist", "notop", "seed") if "-" + key in f}
