@@ -111,6 +111,8 @@ struct vft_ctx {
     std::vector<SweepSlotHost> slots;   // never moves (ensure_slots)
     void *mqBuf = nullptr;        // interleaved queries of the profile-seed groups of a batch (QuerySlot::mq): VFT_MQ_GROUPS groups
     size_t mqGroupBytes = 0;
+    void *lqBuf = nullptr;        // code records of the leaf-seed groups of a batch (QuerySlot::lq): a dword per padded column and group
+    size_t lqGroupBytes = 0;
     char *dMerge = nullptr, *hMerge = nullptr, *hMergeDev = nullptr;   // result blocks of vft_merge_hits_batch
     size_t mergeBytes = 0;
     int32_t hitsCap = 0;
@@ -2321,7 +2323,7 @@ static int sweep_one(vft_ctx *c, int slot, int64_t query, int64_t nActive, int64
 // S leaf seeds - or S profile seeds - of a batch (the seeds at positions slotOf[0 .. S-1] of it) in ONE pass over the targets
 // (k_sweep_nt_leafq_multi / k_sweep_nt_profq_multi): results in the buffers of those slots, bit for bit those of S sweep_one calls.  The caller has checked that no lazy refresh is due (sweep_one's step 1) and has staged the queries.
 template <typename REAL, int S>
-static int sweep_group(vft_ctx *c, bool leafSeeds, const int *slotOf, const int64_t *queries, int64_t nActive, int64_t nDiffAllow, double totdiam, const void *mq) {
+static int sweep_group(vft_ctx *c, bool leafSeeds, const int *slotOf, const int64_t *queries, int64_t nActive, int64_t nDiffAllow, double totdiam, const void *mq, const void *lq) {
     SweepArgs s{};
     s.query = queries[slotOf[0]];
     s.lo = c->shardLo;
@@ -2339,6 +2341,7 @@ static int sweep_group(vft_ctx *c, bool leafSeeds, const int *slotOf, const int6
         c->slots[(size_t) slotOf[q]].nPart = (int) grid;
     }
     M.mq = (const REAL *) mq;
+    M.lq = (const uint32_t *) lq;
     kernel_event(c);
     if (grid && leafSeeds) launch((k_sweep_nt_leafq_multi<REAL, S>), dim3(grid), dim3(VFT_WG), 0, c->stream, arena<REAL>(c), M, s);
     // profile seeds: heavy and table workgroups alike take all S seeds
@@ -2368,7 +2371,7 @@ static bool mixed_sweep_fits(vft_ctx *c) {
 // a full group of leaf seeds and a full group of profile seeds of a batch in ONE pass over the targets (k_sweep_nt_mixed_multi): results
 // bit for bit those of the two sweep_group calls it replaces; same preconditions, and mixed_sweep_fits
 template <typename REAL>
-static int sweep_mixed(vft_ctx *c, const int *leafPos, const int *profPos, const int64_t *queries, int64_t nActive, int64_t nDiffAllow, double totdiam, const void *mq) {
+static int sweep_mixed(vft_ctx *c, const int *leafPos, const int *profPos, const int64_t *queries, int64_t nActive, int64_t nDiffAllow, double totdiam, const void *mq, const void *lq) {
     constexpr int S = 4;
     MixedArgs<REAL, S, S> a;
     memset((void *) &a, 0, sizeof(a));
@@ -2395,7 +2398,9 @@ static int sweep_mixed(vft_ctx *c, const int *leafPos, const int *profPos, const
         c->slots[(size_t) profPos[q]].nPart = (int) gridP;
     }
     a.M.L.mq = nullptr;
+    a.M.L.lq = (const uint32_t *) lq;
     a.M.P.mq = (const REAL *) mq;
+    a.M.P.lq = nullptr;
     kernel_event(c);
     launch((k_sweep_nt_mixed_multi<REAL, S, S>), dim3((unsigned) (a.nInt + a.nLeafHeavy + s.nLeafWG)), dim3(VFT_WG), 0, c->stream, a);
     kernel_event(c);
@@ -2486,21 +2491,25 @@ extern "C" int vft_sweep_batch(vft_ctx *c, int32_t nSeeds, const int64_t *querie
     }
     const int64_t nPosPad = (int64_t) c->d.nChunk * VFT_CHUNK;
     const size_t mqGroupBytes = (size_t) nPosPad * VFT_MQ_STRIDE(4) * c->rs;
-    if (!groups.empty() && !c->mqBuf) {   // (32 groups: the profile seeds of the largest batch, two per group)
-        OWNCHK(own_dev(c, &c->mqBuf, 32 * mqGroupBytes));
+    const size_t lqGroupBytes = (size_t) nPosPad * sizeof(uint32_t);   // (a multiple of 64: a group of 8 columns is 32 aligned bytes)
+    if (!groups.empty() && !c->mqBuf) {   // (32 groups: the seeds of the largest batch, two per group)
+        OWNCHK(own_group(c, [&]() -> int {
+            OWNCHK(own_dev(c, &c->mqBuf, 32 * mqGroupBytes));
+            return own_dev(c, &c->lqBuf, 32 * lqGroupBytes);
+        }));
         c->mqGroupBytes = mqGroupBytes;
+        c->lqGroupBytes = lqGroupBytes;
     }
     if (staged) {
         if (int r = flush_pending(c)) return r;
-        // where a seed's query goes in its group's interleaved buffer (profile-seed groups only)
-        std::vector<int> mqGroup((size_t) nSeeds, -1), mqIdx((size_t) nSeeds, 0), mqS((size_t) nSeeds, 0);
+        // where a seed's query goes in its group's interleaved buffer (profile-seed groups) or code record (leaf-seed groups)
+        std::vector<int> mqGroup((size_t) nSeeds, -1), mqIdx((size_t) nSeeds, 0), mqS((size_t) nSeeds, 0), lqGroup((size_t) nSeeds, -1);
         for (size_t g = 0; g < groups.size(); g++)
-            if (!groups[g].leaf)
-                for (int q = 0; q < groups[g].n; q++) {
-                    mqGroup[(size_t) groups[g].pos[q]] = (int) g;
-                    mqIdx[(size_t) groups[g].pos[q]] = q;
-                    mqS[(size_t) groups[g].pos[q]] = groups[g].n;
-                }
+            for (int q = 0; q < groups[g].n; q++) {
+                (groups[g].leaf ? lqGroup : mqGroup)[(size_t) groups[g].pos[q]] = (int) g;
+                mqIdx[(size_t) groups[g].pos[q]] = q;
+                mqS[(size_t) groups[g].pos[q]] = groups[g].n;
+            }
         Stage st;
         if (int r = st.open(c, (size_t) nSeeds * (c->cfg.precision == 4 ? sizeof(QuerySlot<float>) : sizeof(QuerySlot<double>)), Stage::RING_ONLY)) return r;
         if (c->cfg.precision == 4) {
@@ -2509,8 +2518,9 @@ extern "C" int vft_sweep_batch(vft_ctx *c, int32_t nSeeds, const int64_t *querie
                 qs.node = queries[s];
                 qs.q = qbuf_slot<float>(c, s);
                 qs.mq = mqGroup[(size_t) s] >= 0 ? (float *) ((char *) c->mqBuf + (size_t) mqGroup[(size_t) s] * c->mqGroupBytes) : nullptr;
-                qs.mqIdx = mqIdx[(size_t) s];
-                qs.mqS = mqS[(size_t) s];
+                qs.lq = lqGroup[(size_t) s] >= 0 ? (uint32_t *) ((char *) c->lqBuf + (size_t) lqGroup[(size_t) s] * c->lqGroupBytes) : nullptr;
+                qs.mqIdx = qs.lqIdx = mqIdx[(size_t) s];
+                qs.mqS = qs.lqS = mqS[(size_t) s];
                 st.put((size_t) s * sizeof(qs), &qs, sizeof(qs));
             }
             launch((k_extract_query_batch<float, 4>), dim3(cdiv(nPosPad, 256), (unsigned) nSeeds), dim3(256), 0, c->stream, arena<float>(c), st.dev<const QuerySlot<float>>(0));
@@ -2520,8 +2530,9 @@ extern "C" int vft_sweep_batch(vft_ctx *c, int32_t nSeeds, const int64_t *querie
                 qs.node = queries[s];
                 qs.q = qbuf_slot<double>(c, s);
                 qs.mq = mqGroup[(size_t) s] >= 0 ? (double *) ((char *) c->mqBuf + (size_t) mqGroup[(size_t) s] * c->mqGroupBytes) : nullptr;
-                qs.mqIdx = mqIdx[(size_t) s];
-                qs.mqS = mqS[(size_t) s];
+                qs.lq = lqGroup[(size_t) s] >= 0 ? (uint32_t *) ((char *) c->lqBuf + (size_t) lqGroup[(size_t) s] * c->lqGroupBytes) : nullptr;
+                qs.mqIdx = qs.lqIdx = mqIdx[(size_t) s];
+                qs.mqS = qs.lqS = mqS[(size_t) s];
                 st.put((size_t) s * sizeof(qs), &qs, sizeof(qs));
             }
             launch((k_extract_query_batch<double, 4>), dim3(cdiv(nPosPad, 256), (unsigned) nSeeds), dim3(256), 0, c->stream, arena<double>(c), st.dev<const QuerySlot<double>>(0));
@@ -2539,7 +2550,8 @@ extern "C" int vft_sweep_batch(vft_ctx *c, int32_t nSeeds, const int64_t *querie
             while (gp < groups.size() && !(!groups[gp].leaf && groups[gp].n == 4)) gp++;
             if (gl == groups.size() || gp == groups.size()) break;
             const void *mq = (const void *) ((char *) c->mqBuf + gp * c->mqGroupBytes);
-            if (int r = sweep_mixed<float>(c, groups[gl].pos, groups[gp].pos, queries, nActive, nDiffAllow, totdiam, mq)) return r;
+            const void *lq = (const void *) ((char *) c->lqBuf + gl * c->lqGroupBytes);
+            if (int r = sweep_mixed<float>(c, groups[gl].pos, groups[gp].pos, queries, nActive, nDiffAllow, totdiam, mq, lq)) return r;
             for (int q = 0; q < 4; q++) done[(size_t) groups[gl].pos[q]] = done[(size_t) groups[gp].pos[q]] = 1;
             groupDone[gl++] = groupDone[gp++] = 1;
         }
@@ -2548,9 +2560,10 @@ extern "C" int vft_sweep_batch(vft_ctx *c, int32_t nSeeds, const int64_t *querie
         if (groupDone[g]) continue;
         const SeedGroup &G = groups[g];
         const void *mq = G.leaf ? nullptr : (const void *) ((char *) c->mqBuf + g * c->mqGroupBytes);
+        const void *lq = G.leaf ? (const void *) ((char *) c->lqBuf + g * c->lqGroupBytes) : nullptr;
         int r;
-        if (c->cfg.precision == 4) r = G.n == 4 ? sweep_group<float, 4>(c, G.leaf, G.pos, queries, nActive, nDiffAllow, totdiam, mq) : sweep_group<float, 2>(c, G.leaf, G.pos, queries, nActive, nDiffAllow, totdiam, mq);
-        else r = G.n == 4 ? sweep_group<double, 4>(c, G.leaf, G.pos, queries, nActive, nDiffAllow, totdiam, mq) : sweep_group<double, 2>(c, G.leaf, G.pos, queries, nActive, nDiffAllow, totdiam, mq);
+        if (c->cfg.precision == 4) r = G.n == 4 ? sweep_group<float, 4>(c, G.leaf, G.pos, queries, nActive, nDiffAllow, totdiam, mq, lq) : sweep_group<float, 2>(c, G.leaf, G.pos, queries, nActive, nDiffAllow, totdiam, mq, lq);
+        else r = G.n == 4 ? sweep_group<double, 4>(c, G.leaf, G.pos, queries, nActive, nDiffAllow, totdiam, mq, lq) : sweep_group<double, 2>(c, G.leaf, G.pos, queries, nActive, nDiffAllow, totdiam, mq, lq);
         if (r) return r;
         for (int q = 0; q < G.n; q++) done[(size_t) G.pos[q]] = 1;
     }

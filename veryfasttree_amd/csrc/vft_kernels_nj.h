@@ -89,17 +89,39 @@ __global__ void k_extract_query(Arena<REAL> A, int64_t node, QueryBuf<REAL> q) {
 #define VFT_PLAIN_COLUMNS 1
 #define VFT_MQ_STRIDE(S) (4 * (S) + 8)
 #endif
+// lq (optional): the seed is one of lqS LEAF seeds that share a pass (k_sweep_nt_leafq_multi, k_sweep_nt_mixed_multi) - its reference
+// codes also go, as byte lqIdx, into the group's code record: ONE dword per padded column, byte q = seed q's code.  Unused bytes
+// and padding columns hold NOCODE.  A group of 8 columns is 32 aligned bytes: one scalar load brings every leaf seed's codes where S
+// separate buffers took S pointers (2 S SGPRs held across the column loop) and S loads per four columns (vft_int_chunk_consume_all).
+// -DVFT_NO_SEED_CODE_RECORDS (a variant build, for A/B runs) compiles the record, the one-instruction select masks (vft_ubit_mask)
+// and the leaf seeds' gap skip out: the code pointers, the compiler's masks and the gap product as before.
+#ifdef VFT_NO_SEED_CODE_RECORDS
+#define VFT_SEED_CODE_RECORDS 0
+#else
+#define VFT_SEED_CODE_RECORDS 1
+#endif
 template <typename REAL>
 struct QuerySlot {
     int64_t node;
     QueryBuf<REAL> q;
     REAL *mq;
     int32_t mqIdx, mqS;
+    uint32_t *lq;
+    int32_t lqIdx, lqS;
 };
 template <typename REAL, int NC>
 __global__ void k_extract_query_batch(Arena<REAL> A, const QuerySlot<REAL> *qs) {
     const QuerySlot<REAL> &sl = qs[blockIdx.y];
     vft_extract_query<REAL, NC>(A, sl.node, sl.q);
+    if (VFT_SEED_CODE_RECORDS && NC == 4 && sl.lq) {   // (the seeds of a group write different bytes of a column's dword)
+        const int64_t p = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+        if (p < (int64_t) A.d.nChunk * VFT_CHUNK) {
+            uint8_t *dst = (uint8_t *) (sl.lq + p);
+            dst[sl.lqIdx] = sl.q.code[p];
+            if (sl.lqIdx == 0)
+                for (int k = sl.lqS; k < 4; k++) dst[k] = VFT_NOCODE_;
+        }
+    }
     if (NC == 4 && sl.mq) {   // (the thread re-reads what it has just written: its own column)
         const int64_t p = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
         if (p < (int64_t) A.d.nChunk * VFT_CHUNK) {
@@ -623,6 +645,16 @@ struct MultiLeafQ {
     SweepOut<REAL> O[S];
     int64_t query[S];
     const REAL *mq;   // profile seeds: the S queries' weights and vectors interleaved by column (QuerySlot)
+    const uint32_t *lq;   // leaf seeds: the S queries' reference codes, a dword per column (QuerySlot)
+};
+// all of a leaf seed group the internal-target column loop needs
+template <int S>
+struct LeafCodes {
+#if VFT_SEED_CODE_RECORDS
+    const uint32_t *lq;
+#else
+    const uint8_t *code[S];   // QueryBuf::code of each query
+#endif
 };
 
 template <typename REAL, int SUB>
@@ -720,9 +752,69 @@ __device__ __forceinline__ double vft_usel(double a, double b, unsigned long lon
                             (int) vft_usel_b32((uint32_t) __double2loint(a), (uint32_t) __double2loint(b), mask));
 }
 
-// S queries on one group of SUB columns; code[q] = query q's reference codes (QueryBuf::code) - all of a query the column loop needs
+// The lane mask of a uniform select from ONE bit of a wave-uniform record: bit b of `w`, sign-extended to 64 bits - all ones or zero
+// in one scalar instruction (s_bfe_i64, width 1).  (Written as `(w & bit) ? ~0ull : 0ull` on a code byte the compiler extracts the
+// byte, tests the bit and selects between two 64-bit constants: three to four scalar instructions per mask.)
+__device__ __forceinline__ unsigned long long vft_ubit_mask(unsigned long long w, int b) {   // b: a constant once the loops are unrolled
+    unsigned long long r;
+    asm("s_bfe_i64 %0, %1, %2" : "=s"(r) : "s"(w), "i"((1 << 16) | b) : "scc");   // operand 2: width << 16 | offset
+    return r;
+}
+// f[c] for the wave-uniform code c = 0..3 in bits b, b + 1 of `w`: the two masks and the three selects.  In single precision they are
+// ONE asm statement: behind every asm statement whose result the next instruction reads the compiler puts an s_nop (it cannot see
+// that none of these instructions has a forwarding hazard), two to three per select when mask and selects are statements of their own.
+__device__ __forceinline__ float vft_usel_code(const UVec4<float>::type &f, unsigned long long w, int b) {
+    float r, t;
+    unsigned long long m0, m1;
+    asm("s_bfe_i64 %2, %8, %9\n\t"
+        "s_bfe_i64 %3, %8, %10\n\t"
+        "v_cndmask_b32_e64 %0, %4, %5, %2\n\t"
+        "v_cndmask_b32_e64 %1, %6, %7, %2\n\t"
+        "v_cndmask_b32_e64 %0, %0, %1, %3"
+        : "=&v"(r), "=&v"(t), "=&s"(m0), "=&s"(m1)
+        : "v"(f.x), "v"(f.y), "v"(f.z), "v"(f.w), "s"(w), "i"((1 << 16) | b), "i"((1 << 16) | (b + 1))
+        : "scc");
+    return r;
+}
+__device__ __forceinline__ double vft_usel_code(const UVec4<double>::type &f, unsigned long long w, int b) {
+    const unsigned long long m0 = vft_ubit_mask(w, b), m1 = vft_ubit_mask(w, b + 1);
+    return vft_usel(vft_usel(f.x, f.y, m0), vft_usel(f.z, f.w, m0), m1);
+}
+
+// S queries on one group of SUB columns; lc = the queries' reference codes - all of a query the column loop needs
+// The codes of a group are 8 dwords of the group's code record (QuerySlot::lq), 32 aligned bytes: one scalar load.  Column b's dword
+// is half b & 1 of 64-bit word b >> 1, query q's code byte c starts at bit 8 q of it:
+//     bits 0 and 1 of c, sign-extended, are the two lane masks of the select f_t[c] (vft_ubit_mask);
+//     bit 6 is set for NOCODE (127), a gap of the query, and for no code 0..3.
+// GAPS.  At a gap the pair's weight is +0.0: it adds +0.0 to denom and (+0.0) * piece = +-0.0 (piece is finite) to top, and neither
+// changes a sum that is never -0.0 - the identity of vft_int_chunk_consume.  One forward scalar branch, told to be the rare case, skips
+// the pair; everywhere else the weight is the target's own, no product with a 1.0 / 0.0 factor.
 template <typename REAL, int S, int SUB, bool FENCE = false>
-__device__ __forceinline__ void vft_int_chunk_consume_all(const IntChunkAll<REAL, SUB> &ca, int64_t p0, const uint8_t *const *code, double *top, double *denom) {
+__device__ __forceinline__ void vft_int_chunk_consume_all(const IntChunkAll<REAL, SUB> &ca, int64_t p0, const LeafCodes<S> &lc, double *top, double *denom) {
+#if VFT_SEED_CODE_RECORDS
+    static_assert(SUB == 8, "a group's codes are one 8-dword load");
+    typedef unsigned long long __attribute__((ext_vector_type(4))) vft_ul4_t;
+    const vft_ul4_t rec = *(const __attribute__((address_space(4))) vft_ul4_t *) (lc.lq + p0);   // (p0 is a multiple of 8)
+#pragma unroll
+    for (int b = 0; b < SUB; b++) {
+        if (FENCE) __builtin_amdgcn_sched_barrier(0);   // (a column's temporaries at a time: k_sweep_nt_mixed_multi has no registers to spare)
+        const double wd = (double) ca.w[b];
+        const unsigned long long w2 = b < 2 ? rec.x : b < 4 ? rec.y : b < 6 ? rec.z : rec.w;
+#pragma unroll
+        for (int q = 0; q < S; q++) {
+            const int off = 32 * (b & 1) + 8 * q;   // (< 64 - 8: S <= 4)
+            const uint32_t gap = (uint32_t) (w2 >> (32 * (b & 1))) & (0x40u << (8 * q));   // (one bit of the column's dword)
+            if (__builtin_expect(gap != 0, 0)) continue;   // wave-uniform: a scalar branch
+            const REAL fsel = vft_usel_code(ca.f[b], w2, off);   // f2[cq]
+            const double piece = 1.0 - (double) fsel;
+            denom[q] += wd;
+            top[q] += wd * piece;
+            // (the branch ends a basic block per pair: keep the sums' arithmetic in it - see vft_pin_sums)
+            asm volatile("" : "+v"(top[q]), "+v"(denom[q]));
+        }
+    }
+#else
+    const uint8_t *const *code = lc.code;
 #pragma unroll
     for (int b = 0; b < SUB; b++) {
         if (FENCE) __builtin_amdgcn_sched_barrier(0);   // (a column's temporaries at a time: k_sweep_nt_mixed_multi has no registers to spare)
@@ -740,6 +832,7 @@ __device__ __forceinline__ void vft_int_chunk_consume_all(const IntChunkAll<REAL
             top[q] += wgt * piece;
         }
     }
+#endif
 }
 
 // THE COLUMN LOOP of the multi-seed kernels for one internal target (the lane's; tile = its tile): a group of SUB = 8 columns is decoded
@@ -837,11 +930,15 @@ __global__ __launch_bounds__(VFT_WG) void k_sweep_nt_leafq_multi(Arena<REAL> A, 
             double top[S], denom[S];
 #pragma unroll
             for (int q = 0; q < S; q++) top[q] = denom[q] = 0;
-            const uint8_t *code[S];
+            LeafCodes<S> lc;
+#if VFT_SEED_CODE_RECORDS
+            lc.lq = M.lq;
+#else
 #pragma unroll
-            for (int q = 0; q < S; q++) code[q] = M.Q[q].code;
+            for (int q = 0; q < S; q++) lc.code[q] = M.Q[q].code;
+#endif
             vft_for_column_groups<REAL, SUB>(A, tile, lane, [&](const IntChunkAll<REAL, SUB> &ca, int64_t p0) {
-                vft_int_chunk_consume_all<REAL, S, SUB>(ca, p0, code, top, denom);
+                vft_int_chunk_consume_all<REAL, S, SUB>(ca, p0, lc, top, denom);
             });
 #pragma unroll
             for (int q = 0; q < S; q++) {
@@ -913,6 +1010,9 @@ __device__ __forceinline__ void vft_int_chunk_consume_prof(const IntChunkAll<REA
     for (int b = 0; b < SUB; b++) {
         if (b + 1 < SUB) vft_query_col_load<REAL, S>(nxt, mq, p0 + b + 1);
         __builtin_amdgcn_sched_barrier(0);
+#if VFT_SEED_CODE_RECORDS
+        const unsigned long long cw = VFT_PLAIN_COLUMNS ? cur.codes : 0;   // (the select masks are bits of it: vft_usel_code)
+#endif
 #pragma unroll
         for (int q = 0; q < S; q++) {
             const REAL ww = cur.w[q] * ca.w[b];   // numeric_t product, NJ.tcc:1176
@@ -924,8 +1024,12 @@ __device__ __forceinline__ void vft_int_chunk_consume_prof(const IntChunkAll<REA
             double head = 1.0;
             REAL last;
             if (VFT_PLAIN_COLUMNS) {
+#if VFT_SEED_CODE_RECORDS
+                last = vft_usel_code(ca.f[b], cw, 8 * q);   // f_t[cq]
+#else
                 const unsigned long long m0 = (cur.codes & (1u << (8 * q))) ? ~0ull : 0ull, m1 = (cur.codes & (2u << (8 * q))) ? ~0ull : 0ull;
                 last = vft_usel(vft_usel(ca.f[b].x, ca.f[b].y, m0), vft_usel(ca.f[b].z, ca.f[b].w, m0), m1);   // f_t[cq]
+#endif
             }
             // (told to be the rare case, the vector arm is laid out behind the loop body: a plain column falls through, no branch taken)
             if (!VFT_PLAIN_COLUMNS || __builtin_expect((cur.codes & (0x40u << (8 * q))) != 0, 0)) {   // wave-uniform: a scalar branch
@@ -1222,7 +1326,7 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
 // (nLeafHeavy + nInt) - each seed's range is written completely, by workgroups that serve it.
 //
 // The seeds' buffers and ids (2 x MultiLeafQ) are needed before the column loop (sentinels) and after it (epilogue), the loop itself
-// wants one pointer for the profile seeds (mq) and SL for the leaf seeds (codes).  Passed as a plain kernel argument the compiler loads
+// wants one pointer for the profile seeds (mq) and one for the leaf seeds (lq, their code record).  Passed as a plain kernel argument the compiler loads
 // all of it at the top and keeps it in SGPRs across the loop - more than there are, so they travel through v_writelane / v_readlane
 // inside the loop.  Here the argument block is read through a pointer the compiler cannot see through (vft_kernarg), at the place of
 // use: what the epilogue needs is loaded after the loop.
@@ -1339,14 +1443,18 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
     if (work) {
         // all the column loop needs of the seeds
         const REAL *mq = M1->P.mq;
-        const uint8_t *code[SL];
+        LeafCodes<SL> lc;
+#if VFT_SEED_CODE_RECORDS
+        lc.lq = M1->L.lq;
+#else
 #pragma unroll
-        for (int q = 0; q < SL; q++) code[q] = M1->L.Q[q].code;
+        for (int q = 0; q < SL; q++) lc.code[q] = M1->L.Q[q].code;
+#endif
         vft_for_column_groups<REAL, SUB>(A, tile, lane, [&](const IntChunkAll<REAL, SUB> &ca, int64_t p0) {
             vft_int_chunk_consume_prof<REAL, SP, SUB>(ca, p0, mq, topP, denomP);
             vft_pin_sums<SP>(topP, denomP);
-            __builtin_amdgcn_sched_barrier(0);   // one kind's query scalars live at a time: mq columns, then code bytes
-            vft_int_chunk_consume_all<REAL, SL, SUB, true>(ca, p0, code, topL, denomL);
+            __builtin_amdgcn_sched_barrier(0);   // one kind's query scalars live at a time: mq columns, then the code record
+            vft_int_chunk_consume_all<REAL, SL, SUB, true>(ca, p0, lc, topL, denomL);
             vft_pin_sums<SL>(topL, denomL);
             __builtin_amdgcn_sched_barrier(0);
         });
