@@ -100,6 +100,13 @@ __global__ void k_extract_query(Arena<REAL> A, int64_t node, QueryBuf<REAL> q) {
 #else
 #define VFT_SEED_CODE_RECORDS 1
 #endif
+// -DVFT_NO_GPR_INDEX_SELECT (a variant build, for A/B runs) compiles vft_isel_cvt out: f_t[c] by two masks and three selects
+// (vft_usel_code) in every kernel, as before.  The indexed read takes its index from the code records and replaces the plain path.
+#if defined(VFT_NO_GPR_INDEX_SELECT) || !VFT_SEED_CODE_RECORDS || !VFT_PLAIN_COLUMNS
+#define VFT_GPR_INDEX_SELECT 0
+#else
+#define VFT_GPR_INDEX_SELECT 1
+#endif
 template <typename REAL>
 struct QuerySlot {
     int64_t node;
@@ -781,6 +788,81 @@ __device__ __forceinline__ double vft_usel_code(const UVec4<double>::type &f, un
     return vft_usel(vft_usel(f.x, f.y, m0), vft_usel(f.z, f.w, m0), m1);
 }
 
+#if VFT_GPR_INDEX_SELECT
+// (double) f[c_q & 3] for the S wave-uniform codes c_q in bytes 0 .. S-1 of `cw`, by the VGPR INDEX MODE of gfx9: between
+// s_set_gpr_idx_on and s_set_gpr_idx_off a VALU instruction reads v[src0 + M0[7:0]], so ONE v_cvt_f64_f32 on the first of the four
+// registers selects and converts - where vft_usel_code takes two masks, three selects and the conversion.  (v_movrels_b32 does not
+// exist on gfx950, and the compiler lowers f[c] on a 4-vector to the compare / select chain.)
+// - The four floats of column b of a group sit in FIXED adjacent registers v[VFT_ISEL_V0 + 4 b ...]: a physical-register
+//   constraint is the only way to give the asm text a 32-bit name for the first register of four (a 128-bit operand prints as
+//   v[a:b], which a 32-bit source rejects).  The decode (vft_int_chunk_load_all) writes them there directly: no copies.
+// - The index is the code's low two bits (s_bfe_u32, width 2): a gap or vector byte (127) reads entry 3 as vft_usel_code does, and
+//   its value is unused (a leaf seed's gap skips the pair) or replaced (a profile seed's vector arm).  It never leaves the four.
+// - ONE statement for the S seeds of a column (the compiler puts an s_nop behind every asm statement whose result is read next),
+//   and nothing but the conversions between on and off: the mode indexes src0 of EVERY VALU instruction.  No branch in the
+//   window, and the statement that turns the mode on turns it off.
+// - Spacing: where the compiler itself uses the mode (a uniform index into a register array, gfx950) it emits
+//   `v_pk_add_f32 v[2:3], ..` / `s_set_gpr_idx_on s2, gpr_idx(SRC0)` / `v_mov_b32 v1, v2` / `s_set_gpr_idx_off` / `v_cvt_f64_f32 .., v1`
+//   back to back: no wait state before, inside or behind the window.  The same here.  (The compiler never emits
+//   s_set_gpr_idx_idx; it is the same kind of M0 write as _on, and tests/test_gpu_gpr_index_select.py would see a stale index.)
+// - M0: s_set_gpr_idx_on / _idx write M0[7:0] (and _on M0[15:12]).  The compiler reserves M0 and keeps no value in it across
+//   statements: it writes M0 directly in front of the instruction that reads it (none in the internal workgroups' column loop: no
+//   LDS-DMA, no GWS, no message there; LDS instructions of gfx9 do not read M0).  The clobber tells it all the same; the diagnostic
+//   that a reserved register "may not be preserved" is what is meant, and is silenced for this function alone.  (no instruction of the three kernels names m0.)
+#define VFT_ISEL_V0 64   // first of the 32 registers; below 96 so that k_sweep_nt_profq_multi<float,2> stays within 128
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+#define VFT_ISEL_CASE(B, R0, R1, R2, R3)                                                                                             \
+    case B:                                                                                                                          \
+        if constexpr (S == 4)                                                                                                        \
+            asm("s_bfe_u32 %4, %12, 0x20000\n\t"                                                                                     \
+                "s_bfe_u32 %5, %12, 0x20008\n\t"                                                                                     \
+                "s_bfe_u32 %6, %12, 0x20010\n\t"                                                                                     \
+                "s_bfe_u32 %7, %12, 0x20018\n\t"                                                                                     \
+                "s_set_gpr_idx_on %4, gpr_idx(SRC0)\n\t"                                                                             \
+                "v_cvt_f64_f32_e32 %0, %8\n\t"                                                                                       \
+                "s_set_gpr_idx_idx %5\n\t"                                                                                           \
+                "v_cvt_f64_f32_e32 %1, %8\n\t"                                                                                       \
+                "s_set_gpr_idx_idx %6\n\t"                                                                                           \
+                "v_cvt_f64_f32_e32 %2, %8\n\t"                                                                                       \
+                "s_set_gpr_idx_idx %7\n\t"                                                                                           \
+                "v_cvt_f64_f32_e32 %3, %8\n\t"                                                                                       \
+                "s_set_gpr_idx_off"                                                                                                  \
+                : "=&v"(d[0]), "=&v"(d[1]), "=&v"(d[S - 2]), "=&v"(d[S - 1]), "=&s"(t0), "=&s"(t1), "=&s"(t2), "=&s"(t3)               \
+                : "{" #R0 "}"(f.x), "{" #R1 "}"(f.y), "{" #R2 "}"(f.z), "{" #R3 "}"(f.w), "s"(cw)                                     \
+                : "scc", "m0");                                                                                                      \
+        else                                                                                                                         \
+            asm("s_bfe_u32 %2, %8, 0x20000\n\t"                                                                                      \
+                "s_bfe_u32 %3, %8, 0x20008\n\t"                                                                                      \
+                "s_set_gpr_idx_on %2, gpr_idx(SRC0)\n\t"                                                                             \
+                "v_cvt_f64_f32_e32 %0, %4\n\t"                                                                                       \
+                "s_set_gpr_idx_idx %3\n\t"                                                                                           \
+                "v_cvt_f64_f32_e32 %1, %4\n\t"                                                                                       \
+                "s_set_gpr_idx_off"                                                                                                  \
+                : "=&v"(d[0]), "=&v"(d[1]), "=&s"(t0), "=&s"(t1)                                                                     \
+                : "{" #R0 "}"(f.x), "{" #R1 "}"(f.y), "{" #R2 "}"(f.z), "{" #R3 "}"(f.w), "s"(cw)                                     \
+                : "scc", "m0");                                                                                                      \
+        break;
+template <int S>
+__device__ __forceinline__ void vft_isel_cvt(double *d, const UVec4<float>::type &f, int b, uint32_t cw) {   // b: a constant once the loops are unrolled
+    static_assert(S == 2 || S == 4, "the seed groups of vft_sweep_batch");
+    static_assert(VFT_ISEL_V0 == 64, "the register names below");
+    uint32_t t0, t1, t2, t3;
+    switch (b) {
+        VFT_ISEL_CASE(0, v64, v65, v66, v67)
+        VFT_ISEL_CASE(1, v68, v69, v70, v71)
+        VFT_ISEL_CASE(2, v72, v73, v74, v75)
+        VFT_ISEL_CASE(3, v76, v77, v78, v79)
+        VFT_ISEL_CASE(4, v80, v81, v82, v83)
+        VFT_ISEL_CASE(5, v84, v85, v86, v87)
+        VFT_ISEL_CASE(6, v88, v89, v90, v91)
+        VFT_ISEL_CASE(7, v92, v93, v94, v95)
+    }
+}
+#undef VFT_ISEL_CASE
+#pragma clang diagnostic pop
+#endif
+
 // S queries on one group of SUB columns; lc = the queries' reference codes - all of a query the column loop needs
 // The codes of a group are 8 dwords of the group's code record (QuerySlot::lq), 32 aligned bytes: one scalar load.  Column b's dword
 // is half b & 1 of 64-bit word b >> 1, query q's code byte c starts at bit 8 q of it:
@@ -789,7 +871,10 @@ __device__ __forceinline__ double vft_usel_code(const UVec4<double>::type &f, un
 // GAPS.  At a gap the pair's weight is +0.0: it adds +0.0 to denom and (+0.0) * piece = +-0.0 (piece is finite) to top, and neither
 // changes a sum that is never -0.0 - the identity of vft_int_chunk_consume.  One forward scalar branch, told to be the rare case, skips
 // the pair; everywhere else the weight is the target's own, no product with a 1.0 / 0.0 factor.
-template <typename REAL, int S, int SUB, bool FENCE = false>
+// ISEL: f2[cq] of a column's S seeds by one indexed read each (vft_isel_cvt; single precision, the kernels that place the group's
+// vectors in its registers), in front of the column's pairs - a gapped seed's value is converted and not used.
+// (k_sweep_nt_leafq_multi keeps vft_usel_code: v64..v95 lie beyond its 62 / 70 registers and would cost it two wavefronts per SIMD.)
+template <typename REAL, int S, int SUB, bool FENCE = false, bool ISEL = false>
 __device__ __forceinline__ void vft_int_chunk_consume_all(const IntChunkAll<REAL, SUB> &ca, int64_t p0, const LeafCodes<S> &lc, double *top, double *denom) {
 #if VFT_SEED_CODE_RECORDS
     static_assert(SUB == 8, "a group's codes are one 8-dword load");
@@ -800,13 +885,17 @@ __device__ __forceinline__ void vft_int_chunk_consume_all(const IntChunkAll<REAL
         if (FENCE) __builtin_amdgcn_sched_barrier(0);   // (a column's temporaries at a time: k_sweep_nt_mixed_multi has no registers to spare)
         const double wd = (double) ca.w[b];
         const unsigned long long w2 = b < 2 ? rec.x : b < 4 ? rec.y : b < 6 ? rec.z : rec.w;
+        double fd[S];
+#if VFT_GPR_INDEX_SELECT
+        if constexpr (ISEL) vft_isel_cvt<S>(fd, ca.f[b], b, (uint32_t) (w2 >> (32 * (b & 1))));   // (double) f2[cq], q = 0 .. S-1
+#endif
 #pragma unroll
         for (int q = 0; q < S; q++) {
             const int off = 32 * (b & 1) + 8 * q;   // (< 64 - 8: S <= 4)
             const uint32_t gap = (uint32_t) (w2 >> (32 * (b & 1))) & (0x40u << (8 * q));   // (one bit of the column's dword)
             if (__builtin_expect(gap != 0, 0)) continue;   // wave-uniform: a scalar branch
-            const REAL fsel = vft_usel_code(ca.f[b], w2, off);   // f2[cq]
-            const double piece = 1.0 - (double) fsel;
+            if constexpr (!(VFT_GPR_INDEX_SELECT && ISEL)) fd[q] = (double) vft_usel_code(ca.f[b], w2, off);   // f2[cq]
+            const double piece = 1.0 - fd[q];
             denom[q] += wd;
             top[q] += wd * piece;
             // (the branch ends a basic block per pair: keep the sums' arithmetic in it - see vft_pin_sums)
@@ -1002,7 +1091,9 @@ __device__ __forceinline__ void vft_query_col_load(QueryCol<REAL, S> &c, const R
     }
 }
 
-template <typename REAL, int S, int SUB>
+// ISEL: the plain path's f_t[cq] of a column's S seeds by one indexed read each (vft_isel_cvt, as in vft_int_chunk_consume_all);
+// the vector arm then overrides both operands of piece = head - last, its last = (double) pr.w.
+template <typename REAL, int S, int SUB, bool ISEL = false>
 __device__ __forceinline__ void vft_int_chunk_consume_prof(const IntChunkAll<REAL, SUB> &ca, int64_t p0, const REAL *mq, double *top, double *denom) {
     QueryCol<REAL, S> cur, nxt;
     vft_query_col_load<REAL, S>(cur, mq, p0);
@@ -1013,6 +1104,11 @@ __device__ __forceinline__ void vft_int_chunk_consume_prof(const IntChunkAll<REA
 #if VFT_SEED_CODE_RECORDS
         const unsigned long long cw = VFT_PLAIN_COLUMNS ? cur.codes : 0;   // (the select masks are bits of it: vft_usel_code)
 #endif
+        constexpr bool isel = VFT_GPR_INDEX_SELECT && ISEL;
+        double fd[S];   // isel: (double) f_t[cq], q = 0 .. S-1
+#if VFT_GPR_INDEX_SELECT
+        if constexpr (ISEL) vft_isel_cvt<S>(fd, ca.f[b], b, cur.codes);
+#endif
 #pragma unroll
         for (int q = 0; q < S; q++) {
             const REAL ww = cur.w[q] * ca.w[b];   // numeric_t product, NJ.tcc:1176
@@ -1021,9 +1117,11 @@ __device__ __forceinline__ void vft_int_chunk_consume_prof(const IntChunkAll<REA
             // (a plain code is 0..3, NOCODE - a vector or a gap - is 127: bit 6 of the query's byte tells them apart.  An `if`
             // without an `else` is one forward scalar branch; with two arms the structurised loop pays a flag and two more branches.
             // So the selects run for a vector column too - there cq & 3 = 3 picks f_t[3], replaced at once.)
-            double head = 1.0;
+            double head = 1.0, lastd = 0;
             REAL last;
-            if (VFT_PLAIN_COLUMNS) {
+            if constexpr (isel) {
+                lastd = fd[q];
+            } else if (VFT_PLAIN_COLUMNS) {
 #if VFT_SEED_CODE_RECORDS
                 last = vft_usel_code(ca.f[b], cw, 8 * q);   // f_t[cq]
 #else
@@ -1038,8 +1136,10 @@ __device__ __forceinline__ void vft_int_chunk_consume_prof(const IntChunkAll<REA
                 head -= (double) pr.y;
                 head -= (double) pr.z;
                 last = pr.w;
+                if constexpr (isel) lastd = (double) pr.w;
             }
-            const double piece = head - (double) last;
+            if constexpr (!isel) lastd = (double) last;
+            const double piece = head - lastd;
             denom[q] += wgt;
             top[q] += wgt * piece;
             // (the branch ends a basic block per query: without this the sums' arithmetic sinks below the column's last branch and
@@ -1296,7 +1396,7 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
     if (work) {   // (an internal node: the leaves of a profile query belong to the table workgroups - or, without any, do not exist in [heavyLo, hi))
         const REAL *mq = M1->mq;
         vft_for_column_groups<REAL, SUB>(A, tile, lane, [&](const IntChunkAll<REAL, SUB> &ca, int64_t p0) {
-            vft_int_chunk_consume_prof<REAL, S, SUB>(ca, p0, mq, top, denom);
+            vft_int_chunk_consume_prof<REAL, S, SUB, sizeof(REAL) == 4>(ca, p0, mq, top, denom);
             vft_pin_sums<S>(top, denom);
         });
     }
@@ -1451,10 +1551,10 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
         for (int q = 0; q < SL; q++) lc.code[q] = M1->L.Q[q].code;
 #endif
         vft_for_column_groups<REAL, SUB>(A, tile, lane, [&](const IntChunkAll<REAL, SUB> &ca, int64_t p0) {
-            vft_int_chunk_consume_prof<REAL, SP, SUB>(ca, p0, mq, topP, denomP);
+            vft_int_chunk_consume_prof<REAL, SP, SUB, sizeof(REAL) == 4>(ca, p0, mq, topP, denomP);
             vft_pin_sums<SP>(topP, denomP);
             __builtin_amdgcn_sched_barrier(0);   // one kind's query scalars live at a time: mq columns, then the code record
-            vft_int_chunk_consume_all<REAL, SL, SUB, true>(ca, p0, lc, topL, denomL);
+            vft_int_chunk_consume_all<REAL, SL, SUB, true, sizeof(REAL) == 4>(ca, p0, lc, topL, denomL);
             vft_pin_sums<SL>(topL, denomL);
             __builtin_amdgcn_sched_barrier(0);
         });
