@@ -107,6 +107,14 @@ __global__ void k_extract_query(Arena<REAL> A, int64_t node, QueryBuf<REAL> q) {
 #else
 #define VFT_GPR_INDEX_SELECT 1
 #endif
+// -DVFT_NO_SHARED_PIECES (a variant build, for A/B runs) compiles vft_int_chunk_consume_shared out: 1 - f_t[c] per (seed, column)
+// from an indexed conversion of its own, the two kinds of seed of the mixed kernel one after the other per group, as before.
+// The shared pieces are picked by the index mode: they need VFT_GPR_INDEX_SELECT.
+#if defined(VFT_NO_SHARED_PIECES) || !VFT_GPR_INDEX_SELECT
+#define VFT_SHARED_PIECES 0
+#else
+#define VFT_SHARED_PIECES 1
+#endif
 template <typename REAL>
 struct QuerySlot {
     int64_t node;
@@ -1093,6 +1101,7 @@ __device__ __forceinline__ void vft_query_col_load(QueryCol<REAL, S> &c, const R
 
 // ISEL: the plain path's f_t[cq] of a column's S seeds by one indexed read each (vft_isel_cvt, as in vft_int_chunk_consume_all);
 // the vector arm then overrides both operands of piece = head - last, its last = (double) pr.w.
+// (With VFT_SHARED_PIECES the four-seed kernels in single precision take vft_int_chunk_consume_shared below; two seeds stay here.)
 template <typename REAL, int S, int SUB, bool ISEL = false>
 __device__ __forceinline__ void vft_int_chunk_consume_prof(const IntChunkAll<REAL, SUB> &ca, int64_t p0, const REAL *mq, double *top, double *denom) {
     QueryCol<REAL, S> cur, nxt;
@@ -1150,6 +1159,114 @@ __device__ __forceinline__ void vft_int_chunk_consume_prof(const IntChunkAll<REA
         if (b + 1 < SUB) cur = nxt;
     }
 }
+
+#if VFT_SHARED_PIECES
+// SHARED PIECES.  piece = 1.0 - (double) f_t[c] depends on the target's column and on the code c alone: four values per column, where
+// vft_isel_cvt + the subtraction made one per (seed, column) - eight conversions and eight subtractions in the mixed kernel, each
+// picking one of the same four.  Here a column's four pieces P[k] = 1.0 - (double) f_t[k] are computed ONCE, into eight FIXED adjacent
+// registers v[VFT_PIECE_V0 ..] (four doubles), and a seed's product w * piece reads its piece by the VGPR index mode:
+//     prod_q = v_mul_f64 v[VFT_PIECE_V0 + 2 (c_q & 3) ...], w_q        (IEEE multiplication commutes: the bits of w_q * piece)
+// - the index counts 32-bit registers, so it is twice the code's low two bits; everything else as in vft_isel_cvt (one statement per
+// column and kind of seed, nothing but the S products between on and off, no branch, scc and m0 clobbered; a gap or vector byte reads
+// piece 3, and the product is unused - the leaf seed's gap skips the pair - or replaced by the vector arm's own).
+// The pairs are named in the asm text (a 64-bit operand of the index mode wants the FIRST pair's name) and bound to the four values by
+// physical-register constraints, so the compiler writes `v_add_f64 v[96:97], -v[..], 1.0` straight into them.  96..103: above the
+// decode's registers.  A full group of four seeds only: for two seeds the eight instructions of the pieces outweigh the six they save
+// (k_sweep_nt_profq_multi<float,2>: 284 -> 300 VALU per group), so that kernel keeps vft_int_chunk_consume_prof.
+#define VFT_PIECE_V0 96
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"
+template <int S>
+__device__ __forceinline__ void vft_ipiece_mul(double *prod, double P0, double P1, double P2, double P3, const double *w, uint32_t cw) {
+    static_assert(S == 4, "a full seed group of vft_sweep_batch (for two seeds the four pieces cost more than they save)");
+    static_assert(VFT_PIECE_V0 == 96, "the register names below");
+    uint32_t t0, t1, t2, t3;
+    // 2 (c_q & 3): bits 8 q - 1 .. 8 q + 1 of the dword - bit 7 of a code byte (0..3 or 127) is clear
+    asm("s_lshl_b32 %4, %16, 1\n\t"
+        "s_and_b32 %4, %4, 6\n\t"
+        "s_bfe_u32 %5, %16, 0x30007\n\t"
+        "s_bfe_u32 %6, %16, 0x3000f\n\t"
+        "s_bfe_u32 %7, %16, 0x30017\n\t"
+        "s_set_gpr_idx_on %4, gpr_idx(SRC0)\n\t"
+        "v_mul_f64 %0, v[96:97], %12\n\t"
+        "s_set_gpr_idx_idx %5\n\t"
+        "v_mul_f64 %1, v[96:97], %13\n\t"
+        "s_set_gpr_idx_idx %6\n\t"
+        "v_mul_f64 %2, v[96:97], %14\n\t"
+        "s_set_gpr_idx_idx %7\n\t"
+        "v_mul_f64 %3, v[96:97], %15\n\t"
+        "s_set_gpr_idx_off"
+        : "=&v"(prod[0]), "=&v"(prod[1]), "=&v"(prod[2]), "=&v"(prod[3]), "=&s"(t0), "=&s"(t1), "=&s"(t2), "=&s"(t3)
+        : "{v[96:97]}"(P0), "{v[98:99]}"(P1), "{v[100:101]}"(P2), "{v[102:103]}"(P3), "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "s"(cw)
+        : "scc", "m0");
+}
+#pragma clang diagnostic pop
+
+// SP profile seeds and SL leaf seeds (SL = 0: none, k_sweep_nt_profq_multi) on one group of 8 columns, single precision, ONE COLUMN AT
+// A TIME for both kinds - the pieces live for one column (eight columns' worth would be 64 registers).  Per (seed, target) the
+// operations of vft_int_chunk_consume_prof / vft_int_chunk_consume_all on the same operands in the same order: same bits.
+//   profile seed q:  wgt = (double) (w_q * w_t);  prod = wgt * P[c_q]  - or, out of line, the vector arm's wgt * (((1 - pr.x) - pr.y) - pr.z - pr.w)
+//   leaf seed q:     wd = (double) w_t;           prod = wd * P[c_q]   - a gap skips the pair
+//   both:            denom += w;  top += prod
+// The profile seeds' column scalars (cur / nxt, vft_query_col_load) and the leaf seeds' code record (8 dwords, one load per group) are
+// in scalar registers together; the fences keep a column's temporaries to itself.
+template <int SL, int SP, int SUB>
+__device__ __forceinline__ void vft_int_chunk_consume_shared(const IntChunkAll<float, SUB> &ca, int64_t p0, const float *mq, const uint32_t *lq,
+                                                             double *topP, double *denomP, double *topL, double *denomL) {
+    static_assert(SUB == 8, "a group's codes are one 8-dword load");
+    typedef unsigned long long __attribute__((ext_vector_type(4))) vft_ul4_t;
+    vft_ul4_t rec;
+    if constexpr (SL > 0) rec = *(const __attribute__((address_space(4))) vft_ul4_t *) (lq + p0);   // (p0 is a multiple of 8)
+    QueryCol<float, SP> cur, nxt;
+    vft_query_col_load<float, SP>(cur, mq, p0);
+#pragma unroll
+    for (int b = 0; b < SUB; b++) {
+        if (b + 1 < SUB) vft_query_col_load<float, SP>(nxt, mq, p0 + b + 1);
+        __builtin_amdgcn_sched_barrier(0);
+        const double P0 = 1.0 - (double) ca.f[b].x, P1 = 1.0 - (double) ca.f[b].y, P2 = 1.0 - (double) ca.f[b].z, P3 = 1.0 - (double) ca.f[b].w;
+        {
+            double wgt[SP], prod[SP];
+#pragma unroll
+            for (int q = 0; q < SP; q++) {
+                const float ww = cur.w[q] * ca.w[b];   // numeric_t product, NJ.tcc:1176
+                wgt[q] = (double) ww;
+            }
+            vft_ipiece_mul<SP>(prod, P0, P1, P2, P3, wgt, cur.codes);
+#pragma unroll
+            for (int q = 0; q < SP; q++) {
+                // (told to be the rare case, the vector arm is laid out behind the loop body: a plain column falls through, no branch taken)
+                if (__builtin_expect((cur.codes & (0x40u << (8 * q))) != 0, 0)) {   // wave-uniform: a scalar branch
+                    const UVec4<float>::type pr = cur.f[q] * ca.f[b];   // the four numeric_t products of NJ.tcc:933-937
+                    double head = 1.0 - (double) pr.x;
+                    head -= (double) pr.y;
+                    head -= (double) pr.z;
+                    prod[q] = wgt[q] * (head - (double) pr.w);
+                }
+                denomP[q] += wgt[q];
+                topP[q] += prod[q];
+                asm volatile("" : "+v"(topP[q]), "+v"(denomP[q]));   // (see vft_int_chunk_consume_prof)
+            }
+        }
+        if constexpr (SL > 0) {
+            const unsigned long long w2 = b < 2 ? rec.x : b < 4 ? rec.y : b < 6 ? rec.z : rec.w;
+            const uint32_t cw = (uint32_t) (w2 >> (32 * (b & 1)));   // the column's dword: byte q = seed q's code
+            const double wd = (double) ca.w[b];
+            const double w4[4] = {wd, wd, wd, wd};
+            double prod[SL > 0 ? SL : 1];
+            vft_ipiece_mul<SL>(prod, P0, P1, P2, P3, w4, cw);
+#pragma unroll
+            for (int q = 0; q < SL; q++) {
+                if (__builtin_expect((cw & (0x40u << (8 * q))) != 0, 0)) continue;   // a gap of the seed: wave-uniform, a scalar branch
+                denomL[q] += wd;
+                topL[q] += prod[q];
+                asm volatile("" : "+v"(topL[q]), "+v"(denomL[q]));   // (see vft_int_chunk_consume_all)
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (b + 1 < SUB) cur = nxt;
+    }
+}
+#endif
 
 // ---- the leaf targets of S profile seeds in one walk (round 6): what vft_leaf_table_wg does for one seed - compaction of the span's
 // active leaves, the (column, code) addend table in LDS, one LDS read and two double adds per column - with the compaction, the
@@ -1396,7 +1513,12 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
     if (work) {   // (an internal node: the leaves of a profile query belong to the table workgroups - or, without any, do not exist in [heavyLo, hi))
         const REAL *mq = M1->mq;
         vft_for_column_groups<REAL, SUB>(A, tile, lane, [&](const IntChunkAll<REAL, SUB> &ca, int64_t p0) {
-            vft_int_chunk_consume_prof<REAL, S, SUB, sizeof(REAL) == 4>(ca, p0, mq, top, denom);
+#if VFT_SHARED_PIECES
+            // (four seeds: two seeds' six instructions a column do not pay for the eight of the pieces - 284 -> 300 VALU per group)
+            if constexpr (sizeof(REAL) == 4 && S == 4) vft_int_chunk_consume_shared<0, S, SUB>(ca, p0, mq, nullptr, top, denom, nullptr, nullptr);
+            else
+#endif
+                vft_int_chunk_consume_prof<REAL, S, SUB, sizeof(REAL) == 4>(ca, p0, mq, top, denom);
             vft_pin_sums<S>(top, denom);
         });
     }
@@ -1416,7 +1538,8 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
 
 // ---- SL leaf seeds AND SP profile seeds in one launch (vft_sweep_batch pairs a full group of each): the internal targets are streamed
 // and decoded ONCE - masks and offsets, slots, code byte, weight, vector (vft_int_chunk_load_all) - and both kinds of seed are evaluated
-// on the decoded columns, the profile seeds first (vft_int_chunk_consume_prof), then the leaf seeds (vft_int_chunk_consume_all); per
+// on the decoded columns - column by column, on the column's four shared pieces (vft_int_chunk_consume_shared; without
+// VFT_SHARED_PIECES a group's profile seeds first, vft_int_chunk_consume_prof, then its leaf seeds, vft_int_chunk_consume_all); per
 // (seed, target) the operations are those of the per-kind kernels, in their order: same bits.  Workgroups, in launch order:
 //   1. nInt "internal" ones over [s.heavyLo, s.hi), highest ids first, ids >= s.leafEnd only: all SL + SP seeds
 //   2. nLeafHeavy over [s.lo, s.leafEnd), a leaf per lane: the leaf seeds' popcount distances (k_sweep_nt_leafq_multi's leaf targets)
@@ -1551,6 +1674,15 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
         for (int q = 0; q < SL; q++) lc.code[q] = M1->L.Q[q].code;
 #endif
         vft_for_column_groups<REAL, SUB>(A, tile, lane, [&](const IntChunkAll<REAL, SUB> &ca, int64_t p0) {
+#if VFT_SHARED_PIECES
+            if constexpr (sizeof(REAL) == 4) {   // both kinds column by column, on the column's four shared pieces
+                vft_int_chunk_consume_shared<SL, SP, SUB>(ca, p0, mq, lc.lq, topP, denomP, topL, denomL);
+                vft_pin_sums<SP>(topP, denomP);
+                vft_pin_sums<SL>(topL, denomL);
+                __builtin_amdgcn_sched_barrier(0);
+                return;
+            }
+#endif
             vft_int_chunk_consume_prof<REAL, SP, SUB, sizeof(REAL) == 4>(ca, p0, mq, topP, denomP);
             vft_pin_sums<SP>(topP, denomP);
             __builtin_amdgcn_sched_barrier(0);   // one kind's query scalars live at a time: mq columns, then the code record
