@@ -2247,6 +2247,18 @@ static int run_select(vft_ctx *c, int K, const int64_t *queries, int64_t lo, int
     return VFT_OK;
 }
 
+#ifdef VFT_SELECT_PHASES   // tools-only build (tools/select_phases.py): never in the product library
+// the phase clocks of the last selection: out[VFT_SELPH_ROWS][VFT_SELPH_SEEDS][VFT_SELPH_MARKS] (100 MHz ticks); the device copy is zeroed
+extern "C" int vft_debug_select_phases(vft_ctx *c, unsigned long long *out, int64_t nOut) {
+    if (nOut != (int64_t) VFT_SELPH_ROWS * VFT_SELPH_SEEDS * VFT_SELPH_MARKS) return fail(c, VFT_ERR_INVALID, "vft_debug_select_phases: %d x %d x %d words", VFT_SELPH_ROWS, VFT_SELPH_SEEDS, VFT_SELPH_MARKS);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyFromSymbol(out, HIP_SYMBOL(vft_selph), sizeof(vft_selph)));
+    static const unsigned long long zero[VFT_SELPH_ROWS][VFT_SELPH_SEEDS][VFT_SELPH_MARKS] = {};
+    HIPCHK(c, hipMemcpyToSymbol(HIP_SYMBOL(vft_selph), zero, sizeof(zero)));
+    return VFT_OK;
+}
+#endif
+
 // the lazy refresh, query staging and sweep kernels of ONE seed; its results go to the buffers of `slot`
 static int sweep_one(vft_ctx *c, int slot, int64_t query, int64_t nActive, int64_t nDiffAllow, double totdiam, bool staged = false) {
     if (int r = flush_pending(c)) return r;

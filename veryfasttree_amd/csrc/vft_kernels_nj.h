@@ -2464,6 +2464,27 @@ __global__ __launch_bounds__(VFT_WG) void k_leaf_block(Arena<REAL> A, const int6
 #define VFT_SEL_WGS 128
 #define VFT_CAND_CAP 8192
 
+// Phase clocks of the selection kernels (tools/select_phases.py) exist only in builds made with -DVFT_SELECT_PHASES (a variant build,
+// veryfasttree_amd/build.py); in the product build the marks are nothing.  A mark is thread 0's wall_clock64() (100 MHz) at a phase
+// boundary, stored with an ordinary vector store: workgroup (0, seed) of each kernel, and in the rank sort the seed's last workgroup too.
+#ifdef VFT_SELECT_PHASES
+#define VFT_SELPH_ROWS 4    // hist, collect, rank (workgroup 0), rank (the seed's last workgroup)
+#define VFT_SELPH_SEEDS 16
+#define VFT_SELPH_MARKS 8
+__device__ unsigned long long vft_selph[VFT_SELPH_ROWS][VFT_SELPH_SEEDS][VFT_SELPH_MARKS];
+#define VFT_SELPH(row, mark)                                                                                           \
+    do {                                                                                                               \
+        if (threadIdx.x == 0 && (blockIdx.x == 0 || (row) == 3) && blockIdx.y < VFT_SELPH_SEEDS)                       \
+            vft_selph[row][blockIdx.y][mark] = wall_clock64();                                                         \
+    } while (0)
+#define VFT_SELPH_USE(x) asm volatile("" ::"v"(x))                           // the mark behind it waits for the load of x
+#define VFT_SELPH_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")   // ... for everything this wavefront has issued
+#else
+#define VFT_SELPH(row, mark) ((void) 0)
+#define VFT_SELPH_USE(x) ((void) 0)
+#define VFT_SELPH_DRAIN() ((void) 0)
+#endif
+
 struct SelectState {
     double lo, scale;            // VK(x) = (x - lo) * scale, scale = 1024 * 2^40 / (max - min) (slightly shrunk)
     unsigned long long prefix;   // digits chosen so far (VK >> (shift + 10) must equal it to be binned)
@@ -2514,32 +2535,141 @@ __global__ void k_select_refine(const SelSlot *slots) {
     S->rankDone = 0;
 }
 
-// VFT_SEL_WGS workgroups, each writes its own histogram slice (plain stores).  first: round one - the key range comes from the
-// sweep's per-workgroup (min, max) criteria, which EVERY workgroup reduces for itself (min and max are exact: all of them arrive at the
-// same two numbers, a few microseconds of L2 reads side by side instead of a one-workgroup launch in front), and workgroup 0 sets the
-// selection's state up for the kernels that follow.
+// How the two passes over the criteria (k_select_hist, k_select_collect) read their seed's [lo, hi): as 16-byte vectors - four floats or
+// two doubles on consecutive ids - VFT_SEL_BATCH of them per thread issued back to back BEFORE anything waits (the passes are chains of
+// memory round trips, not bandwidth: section 4.6j of DESIGN.md).  Vector v of the span goes to thread v % (workgroups x VFT_WG); at the
+// 1.25 M ids of the bench step a thread's whole share (<= 10 vectors) is one batch, larger spans loop over batches.  lo is a multiple of
+// 64 (vft_set_shard), so the first vector is aligned; whatever is not a whole aligned vector - at most N - 1 ids in front (none today)
+// and N - 1 behind - is read as scalars, one per thread of the last workgroup.
+// The arrays come as pointers read from a SelSlot: generic ones to the compiler, and a flat load counts as LDS traffic too (lgkmcnt) -
+// every wait for the LDS would drain the loads in flight.  They are device memory: VFT_GLOBAL says so, and the loads are global_load.
+#define VFT_SEL_BATCH 10
+#define VFT_GLOBAL __attribute__((address_space(1)))
 template <typename REAL>
-__global__ __launch_bounds__(VFT_WG) void k_select_hist(const SelSlot *slots, int64_t lo, int64_t hi, int first) {
+struct SelVec {
+    static constexpr int N = 16 / (int) sizeof(REAL);
+    typedef REAL type __attribute__((ext_vector_type(16 / sizeof(REAL))));
+};
+template <typename REAL>
+struct SelSpan {
+    static constexpr int N = SelVec<REAL>::N;
+    typedef typename SelVec<REAL>::type V;
+    const VFT_GLOBAL REAL *crit;
+    const VFT_GLOBAL V *vp;   // the first whole vector; its id is `first`
+    const VFT_GLOBAL V *spare;   // 16 readable bytes for the lanes that have nothing to load
+    int64_t lo, hi, first, nVec, stride, v0;
+    __device__ __forceinline__ SelSpan(const REAL *crit_, int64_t lo_, int64_t hi_, const void *spare_)
+        : crit((const VFT_GLOBAL REAL *) crit_), spare((const VFT_GLOBAL V *) spare_), lo(lo_), hi(hi_ > lo_ ? hi_ : lo_) {
+        const int64_t head = (N - (lo & (N - 1))) & (N - 1);
+        first = lo + head < hi ? lo + head : hi;
+        nVec = (hi - first) / N;
+        vp = (const VFT_GLOBAL V *) (crit + first);
+        stride = (int64_t) gridDim.x * VFT_WG;
+        v0 = (int64_t) blockIdx.x * VFT_WG + threadIdx.x;
+    }
+    // the thread's vectors of the batch that starts at vector vb (a multiple of VFT_SEL_BATCH * stride).
+    // No branch around a load - a lane beyond the span reads the spare bytes, which consume() drops - so that the compiler can COUNT the
+    // loads in flight: what was issued before the batch is waited for with vmcnt(n), not with vmcnt(0).
+    __device__ __forceinline__ void load(int64_t vb, V (&c)[VFT_SEL_BATCH]) const {
+#pragma unroll
+        for (int u = 0; u < VFT_SEL_BATCH; u++) {
+            const int64_t v = vb + v0 + (int64_t) u * stride;
+            c[u] = *(v < nVec ? vp + v : spare);
+        }
+    }
+    // The batch is consumed by a loop that is NOT unrolled: each turn takes the first vector and moves the others one place down (nine
+    // register moves of a vector).  These kernels run each instruction once or ten times and start with a cold instruction cache: forty
+    // copies of the per-element code cost more in instruction fetches than the moves do.  f(id of the vector's first element, vector);
+    // a vector beyond the span arrives as skipped values (1e20).
+    template <typename F>
+    __device__ __forceinline__ void consume(int64_t vb, V (&c)[VFT_SEL_BATCH], F f) const {
+        int64_t v = vb + v0;
+#pragma unroll 1
+        for (int u = 0; u < VFT_SEL_BATCH; u++, v += stride) {
+            V x = c[0];
+#pragma unroll
+            for (int w = 0; w + 1 < VFT_SEL_BATCH; w++) c[w] = c[w + 1];
+#pragma unroll
+            for (int e = 0; e < N; e++) x[e] = v < nVec ? x[e] : (REAL) 1e20;
+            f(first + v * N, x);
+        }
+    }
+    // the scalar edges: thread t of the last workgroup takes id lo + t in front of the vectors (t < N - 1) or the (t - (N - 1))-th behind
+    __device__ __forceinline__ REAL load_edge(int64_t &j) const {
+        const int64_t t = threadIdx.x;
+        const int64_t e = t < N - 1 ? lo + t : first + nVec * N + (t - (N - 1));
+        const bool ok = blockIdx.x == gridDim.x - 1 && t < 2 * (N - 1) && (t < N - 1 ? e < first : e < hi);
+        const REAL x = *(ok ? crit + e : (const VFT_GLOBAL REAL *) spare);
+        j = ok ? e : -1;
+        return ok ? x : (REAL) 1e20;
+    }
+};
+
+// VFT_SEL_WGS workgroups, one LDS histogram each.  first: round one - the key range comes from the
+// sweep's per-workgroup (min, max) criteria, which EVERY workgroup reduces for itself (min and max are exact: all of them arrive at the
+// same two numbers, L2 reads side by side instead of a one-workgroup launch in front), and workgroup 0 sets the
+// selection's state up for the kernels that follow.  Every load the kernel makes before its epilogue - the (min, max) pairs as 16-byte
+// vectors and the thread's first batch of criteria - is issued before the first wait.
+#define VFT_SEL_PART_BATCH 5
+template <typename REAL>
+__global__ __launch_bounds__(VFT_WG, 4) void k_select_hist(const SelSlot *slots, int64_t lo, int64_t hi, int first) {
     const SelSlot &sl = slots[blockIdx.y];
     const REAL *crit = (const REAL *) sl.crit;
     SelectState *S = sl.sel;
     unsigned int *slices = sl.slices;
+    typedef typename SelVec<REAL>::type V;
+    constexpr int N = SelVec<REAL>::N;
+    const SelSpan<REAL> sp(crit, lo, hi, sl.slices);
     // four copies of the histogram, one per lane modulo 4: the criteria of a sweep crowd into a few digits, and LDS atomics of a
     // wavefront on one address run one after the other
     __shared__ unsigned int lh4[4][VFT_NBINS];
     unsigned int *lh = lh4[threadIdx.x & 3];
     __shared__ double smin[VFT_WG / 64], smax[VFT_WG / 64];
+    VFT_SELPH(0, 0);
+    // ---- issue: the first batch of the (min, max) pairs, then the thread's first batch of criteria; nothing waits before the LDS is zero
+    const VFT_GLOBAL REAL *partMin = (const VFT_GLOBAL REAL *) sl.partMin, *partMax = (const VFT_GLOBAL REAL *) sl.partMax;
+    const int nPart = first ? sl.nPart : 0, nPartVec = nPart / N;
+    V pa[VFT_SEL_PART_BATCH], pb[VFT_SEL_PART_BATCH];
+    auto load_parts = [&](int p0) {
+#pragma unroll
+        for (int u = 0; u < VFT_SEL_PART_BATCH; u++) {
+            const int p = p0 + u * VFT_WG + (int) threadIdx.x;   // (beyond the last whole vector: spare bytes, dropped in fold_parts)
+            pa[u] = *(p < nPartVec ? (const VFT_GLOBAL V *) partMin + p : sp.spare);
+            pb[u] = *(p < nPartVec ? (const VFT_GLOBAL V *) partMax + p : sp.spare);
+        }
+    };
+    load_parts(0);
+    // the pairs behind the last whole vector (nPart is arbitrary); a thread without one reads pair 0 for nothing - no branch, no wait
+    const int pt = nPartVec * N + (int) threadIdx.x < nPart ? nPartVec * N + (int) threadIdx.x : 0;
+    const REAL pta = partMin[pt], ptb = partMax[pt];
+    V c[VFT_SEL_BATCH];
+    sp.load(0, c);
+    int64_t je;
+    const REAL ce = sp.load_edge(je);
     for (int t = threadIdx.x; t < 4 * VFT_NBINS; t += VFT_WG) lh4[0][t] = 0;
     double vlo, scale;
     unsigned long long prefix;
     unsigned int level;
     if (first) {
-        const REAL *partMin = (const REAL *) sl.partMin, *partMax = (const REAL *) sl.partMax;
         double cmin = 1e30, cmax = -1e30;
-        for (int t = threadIdx.x; t < sl.nPart; t += VFT_WG) {
-            const double a = (double) partMin[t], b = (double) partMax[t];
-            cmin = a < cmin ? a : cmin;
-            cmax = b > cmax ? b : cmax;
+        auto fold_parts = [&](int p0) {
+#pragma unroll
+            for (int u = 0; u < VFT_SEL_PART_BATCH; u++) {
+                const bool in = p0 + u * VFT_WG + (int) threadIdx.x < nPartVec;
+#pragma unroll
+                for (int e = 0; e < N; e++) {
+                    const double a = (double) pa[u][e], b = (double) pb[u][e];
+                    cmin = in && a < cmin ? a : cmin;
+                    cmax = in && b > cmax ? b : cmax;
+                }
+            }
+        };
+        fold_parts(0);   // (the first batch is all of them up to 5 x 256 vectors: the mixed pass of the bench step has 4 884 pairs)
+        cmin = (double) pta < cmin ? (double) pta : cmin;   // (pair 0 again, or a pair of the tail: a pair either way)
+        cmax = (double) ptb > cmax ? (double) ptb : cmax;
+        for (int p0 = VFT_SEL_PART_BATCH * VFT_WG; p0 < nPartVec; p0 += VFT_SEL_PART_BATCH * VFT_WG) {
+            load_parts(p0);
+            fold_parts(p0);
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {
@@ -2582,28 +2712,26 @@ __global__ __launch_bounds__(VFT_WG) void k_select_hist(const SelSlot *slots, in
         level = S->level;
     }
     const unsigned int shift = vft_level_shift(level);
-    const int64_t stride = (int64_t) gridDim.x * VFT_WG;
-    int64_t j = lo + (int64_t) blockIdx.x * VFT_WG + threadIdx.x;
-    for (; j + 3 * stride < hi; j += 4 * stride) {   // four independent loads in flight per thread
-        REAL c[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) c[u] = crit[j + u * stride];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            if (c[u] < (REAL) 1e20) {
-                const unsigned long long vk = vft_vk((double) c[u], vlo, scale);
-                if ((vk >> (shift + VFT_DIGIT_BITS)) == prefix) atomicAdd(&lh[(vk >> shift) & (VFT_NBINS - 1)], 1u);
-            }
-        }
-    }
-    for (; j < hi; j += stride) {
-        const REAL c = crit[j];
-        if (c < (REAL) 1e20) {
-            const unsigned long long vk = vft_vk((double) c, vlo, scale);
+    VFT_SELPH_USE(scale);
+    VFT_SELPH(0, 1);
+    auto bin = [&](REAL x) {
+        if (x < (REAL) 1e20) {
+            const unsigned long long vk = vft_vk((double) x, vlo, scale);
             if ((vk >> (shift + VFT_DIGIT_BITS)) == prefix) atomicAdd(&lh[(vk >> shift) & (VFT_NBINS - 1)], 1u);
         }
+    };
+    bin(ce);
+    for (int64_t vb = 0;;) {
+        sp.consume(vb, c, [&](int64_t, const V &x) {
+#pragma unroll
+            for (int e = 0; e < N; e++) bin(x[e]);
+        });
+        vb += VFT_SEL_BATCH * sp.stride;
+        if (vb >= sp.nVec) break;
+        sp.load(vb, c);
     }
     __syncthreads();
+    VFT_SELPH(0, 2);
     // into the seed's ONE histogram (round 6; zero on entry: k_select_rank's last workgroup leaves it so): the bins this workgroup touched,
     // one global atomic each - the threshold digit is then found by every workgroup of k_select_collect for itself (4 KB, one scan)
     // instead of by a one-workgroup launch over VFT_SEL_WGS slices in between
@@ -2611,10 +2739,12 @@ __global__ __launch_bounds__(VFT_WG) void k_select_hist(const SelSlot *slots, in
         const unsigned int v = lh4[0][t] + lh4[1][t] + lh4[2][t] + lh4[3][t];
         if (v) atomicAdd(&slices[t], v);
     }
+    VFT_SELPH_DRAIN();
+    VFT_SELPH(0, 3);
 }
 
 template <typename REAL>
-__global__ __launch_bounds__(VFT_WG) void k_select_collect(const SelSlot *slots, int64_t lo, int64_t hi, unsigned int k) {
+__global__ __launch_bounds__(VFT_WG, 4) void k_select_collect(const SelSlot *slots, int64_t lo, int64_t hi, unsigned int k) {
     const SelSlot &sl = slots[blockIdx.y];
     const REAL *crit = (const REAL *) sl.crit;
     SelectState *S = sl.sel;
@@ -2624,20 +2754,35 @@ __global__ __launch_bounds__(VFT_WG) void k_select_collect(const SelSlot *slots,
     __shared__ uint64_t lkey[VFT_CAND_CAP / 8];
     __shared__ int32_t lid[VFT_CAND_CAP / 8];
     if (threadIdx.x == 0) lcount = 0;
+    VFT_SELPH(1, 0);
+    // ---- issue everything the kernel reads, before anything waits: the selection's state (nothing this kernel reads from it is written
+    //      by this kernel), this thread's four words of the histogram, its first batch of criteria
+    typedef typename SelVec<REAL>::type V;
+    constexpr int N = SelVec<REAL>::N;
+    const SelSpan<REAL> sp(crit, lo, hi, sl.slices);
+    const VFT_GLOBAL SelectState *Sg = (const VFT_GLOBAL SelectState *) S;
+    const unsigned int nIn = Sg->nIn;
+    const double vlo = Sg->lo, scale = Sg->scale;
+    const unsigned long long prefix = Sg->prefix;
+    const unsigned int shift = vft_level_shift(Sg->level);
+    static_assert(VFT_NBINS / VFT_WG == 4, "a thread's share of the histogram is one 16-byte vector");
+    typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
+    const u4_t gh4 = ((const VFT_GLOBAL u4_t *) sl.slices)[threadIdx.x];
+    V c[VFT_SEL_BATCH];
+    sp.load(0, c);
+    int64_t je;
+    const REAL ce = sp.load_edge(je);
     // ---- the digit that holds the need-th smallest value, from the seed's histogram (every workgroup for itself: the same 1 024
     //      numbers, the same answer; workgroup 0 leaves it in the state for a refinement round and the diagnostics)
     __shared__ unsigned int wsum[VFT_WG / 64], sTb, sBelow, sThresh;
     unsigned int tb;
     {
         constexpr int PER = VFT_NBINS / VFT_WG;
-        const unsigned int *gh = sl.slices;
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        unsigned int v[PER], mine = 0;
+        const unsigned int v[PER] = {gh4.x, gh4.y, gh4.z, gh4.w};
+        unsigned int mine = 0;
 #pragma unroll
-        for (int u = 0; u < PER; u++) {
-            v[u] = gh[threadIdx.x * PER + u];
-            mine += v[u];
-        }
+        for (int u = 0; u < PER; u++) mine += v[u];
         unsigned int incl = mine;
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) {
@@ -2657,7 +2802,7 @@ __global__ __launch_bounds__(VFT_WG) void k_select_collect(const SelSlot *slots,
             if (w < wave) before += wsum[w];
             total += wsum[w];
         }
-        unsigned int need = k > S->nIn ? k - S->nIn : 0;
+        unsigned int need = k > nIn ? k - nIn : 0;
         if (need > total) need = total;
         if (need > 0 && before < need && before + mine >= need) {   // exactly one thread
             unsigned int b = before;
@@ -2679,10 +2824,10 @@ __global__ __launch_bounds__(VFT_WG) void k_select_collect(const SelSlot *slots,
             S->nThresh = sThresh;
         }
     }
-    const double vlo = S->lo, scale = S->scale;
-    const unsigned long long prefix = S->prefix;
-    const unsigned int shift = vft_level_shift(S->level);
-    const int64_t stride = (int64_t) gridDim.x * VFT_WG;
+    VFT_SELPH(1, 1);
+    VFT_SELPH_USE(scale);
+    VFT_SELPH_USE(shift);
+    VFT_SELPH(1, 2);
     auto take = [&](int64_t j, REAL c) {
         if (!(c < (REAL) 1e20)) return;
         const unsigned long long vk = vft_vk((double) c, vlo, scale);
@@ -2696,16 +2841,18 @@ __global__ __launch_bounds__(VFT_WG) void k_select_collect(const SelSlot *slots,
             }
         }
     };
-    int64_t j = lo + (int64_t) blockIdx.x * VFT_WG + threadIdx.x;
-    for (; j + 3 * stride < hi; j += 4 * stride) {   // four independent loads in flight per thread
-        REAL c[4];
+    take(je, ce);
+    for (int64_t vb = 0;;) {
+        sp.consume(vb, c, [&](int64_t j, const V &x) {
 #pragma unroll
-        for (int u = 0; u < 4; u++) c[u] = crit[j + u * stride];
-#pragma unroll
-        for (int u = 0; u < 4; u++) take(j + u * stride, c[u]);
+            for (int e = 0; e < N; e++) take(j + e, x[e]);
+        });
+        vb += VFT_SEL_BATCH * sp.stride;
+        if (vb >= sp.nVec) break;
+        sp.load(vb, c);
     }
-    for (; j < hi; j += stride) take(j, crit[j]);
     __syncthreads();
+    VFT_SELPH(1, 3);
     const unsigned int n = lcount;
     if (n > VFT_CAND_CAP / 8) {
         if (threadIdx.x == 0) S->overflow = 1;
@@ -2713,6 +2860,7 @@ __global__ __launch_bounds__(VFT_WG) void k_select_collect(const SelSlot *slots,
     }
     if (threadIdx.x == 0) lbase = n ? atomicAdd(&S->nCand, n) : 0;   // one global atomic per workgroup
     __syncthreads();
+    VFT_SELPH(1, 4);
     const unsigned int base = lbase;
     if (base + n > VFT_CAND_CAP) {
         if (threadIdx.x == 0) S->overflow = 1;
@@ -2722,6 +2870,8 @@ __global__ __launch_bounds__(VFT_WG) void k_select_collect(const SelSlot *slots,
         candKey[base + t] = lkey[t];
         candId[base + t] = lid[t];
     }
+    VFT_SELPH_DRAIN();
+    VFT_SELPH(1, 5);
 }
 
 // What the host reads back after a sweep: one small block, one copy, one synchronisation.
@@ -2776,47 +2926,87 @@ __global__ __launch_bounds__(VFT_WG) void k_select_rank(const SelSlot *slots, in
     HIT *hostHits = (HIT *) sl.hostHits;
     __shared__ uint64_t sk[VFT_RANK_TILE];
     __shared__ int32_t si[VFT_RANK_TILE];
+    VFT_SELPH(2, 0);
     // An overflowed collection (more candidates than the buffer takes: the host narrows the key range and repeats) has counted
     // candidates it never stored - those entries hold whatever the memory held before, and an id read from there indexed the
     // result arrays (a memory access fault once the allocator handed out recycled blocks: the seed batches of a second tree in
     // one process).  Its records are discarded anyway: rank nothing, publish empty records and the overflow flag.
-    const unsigned int n = S->overflow ? 0u : (S->nCand < VFT_CAND_CAP ? S->nCand : VFT_CAND_CAP);
+    // The first trip: nCand and overflow are neighbours in the state (one 8-byte load), and this thread's own candidate goes out
+    // with them, before n is known - the buffers hold VFT_CAND_CAP entries, an entry nobody stored is read and dropped below.
+    static_assert(offsetof(SelectState, nCand) % 8 == 0 && offsetof(SelectState, overflow) == offsetof(SelectState, nCand) + 4,
+                  "nCand and overflow are read as one word");
     const unsigned int perWg = VFT_WG / VFT_RANK_LANES;
-    const unsigned int span = n > (unsigned int) k ? n : (unsigned int) k;
-    if (blockIdx.x * perWg >= span) return;   // whole workgroup idle (not counted below)
     const unsigned int cand = blockIdx.x * perWg + threadIdx.x / VFT_RANK_LANES;
     const unsigned int sub = threadIdx.x % VFT_RANK_LANES;
+    unsigned long long candOver;
+    __builtin_memcpy(&candOver, &S->nCand, 8);
+    const uint64_t key0 = cand < VFT_CAND_CAP ? candKey[cand] : 0;
+    const int32_t id0 = cand < VFT_CAND_CAP ? candId[cand] : 0;
+    const unsigned int nCand = (unsigned int) candOver, overflow = (unsigned int) (candOver >> 32);
+    const unsigned int n = overflow ? 0u : (nCand < VFT_CAND_CAP ? nCand : VFT_CAND_CAP);
+    const unsigned int span = n > (unsigned int) k ? n : (unsigned int) k;
+    if (blockIdx.x * perWg >= span) return;   // whole workgroup idle (not counted below)
+    VFT_SELPH(2, 1);
     const bool mine = cand < n;
-    const uint64_t myKey = mine ? candKey[cand] : 0;
-    const int32_t myId = mine ? candId[cand] : 0;
+    const uint64_t myKey = mine ? key0 : 0;
+    const int32_t myId = mine ? id0 : 0;
+    // the record's numbers need the id alone: the gathers go out now, with the staging loads, and arrive under the compare loop (n
+    // exceeds k by a percent or two: a few of them are for nothing)
+    REAL myDist = 0, myWeight = 0, myCrit = 0;
+    if (mine && sub == 0) {
+        myDist = dist[myId];
+        myWeight = weight[myId];
+        myCrit = crit[myId];
+    }
+    // Single precision: the key is 32 bits wide (vft_order_f32), so key and id make ONE 64-bit word whose unsigned order is the
+    // records' order - key in the high half, 2^32 - 1 - id in the low half (a larger id comes first) - and the compare loop, the longest
+    // phase of the kernel (section 4.6j), is one LDS read and one comparison per candidate instead of two reads and three comparisons.
+    // No two candidates share a word (ids differ), a candidate does not precede itself either way, padding (~0) precedes nobody.
+    constexpr bool PACKED = sizeof(REAL) == 4;
+    auto packed = [](uint64_t key, int32_t id) -> uint64_t { return (key << 32) | (uint64_t) (0xFFFFFFFFu - (uint32_t) id); };
+    const uint64_t myWord = packed(myKey, myId);
     unsigned int rank = 0;
     for (unsigned int base = 0; base < n; base += VFT_RANK_TILE) {
         __syncthreads();
         for (unsigned int u = threadIdx.x; u < VFT_RANK_TILE; u += VFT_WG) {
-            sk[u] = base + u < n ? candKey[base + u] : ~0ull;
-            si[u] = base + u < n ? candId[base + u] : -1;
+            const uint64_t ku = base + u < n ? candKey[base + u] : ~0ull;
+            const int32_t iu = base + u < n ? candId[base + u] : -1;
+            if (PACKED) {
+                sk[u] = base + u < n ? packed(ku, iu) : ~0ull;
+            } else {
+                sk[u] = ku;
+                si[u] = iu;
+            }
         }
         __syncthreads();
+        VFT_SELPH(2, 2);
         const unsigned int lim = n - base < VFT_RANK_TILE ? n - base : VFT_RANK_TILE;
         if (mine) {
+            if (PACKED) {
 #pragma unroll 8
-            for (unsigned int u = sub; u < lim; u += VFT_RANK_LANES) {
-                const uint64_t ku = sk[u];
-                const int32_t iu = si[u];
-                // u precedes me: smaller key, or equal key and larger id
-                rank += (ku < myKey || (ku == myKey && iu > myId)) ? 1u : 0u;
+                for (unsigned int u = sub; u < lim; u += VFT_RANK_LANES) rank += sk[u] < myWord ? 1u : 0u;
+            } else {
+#pragma unroll 8
+                for (unsigned int u = sub; u < lim; u += VFT_RANK_LANES) {
+                    const uint64_t ku = sk[u];
+                    const int32_t iu = si[u];
+                    // u precedes me: smaller key, or equal key and larger id
+                    rank += (ku < myKey || (ku == myKey && iu > myId)) ? 1u : 0u;
+                }
             }
         }
     }
 #pragma unroll
     for (int off = VFT_RANK_LANES / 2; off > 0; off >>= 1) rank += __shfl_xor(rank, off, VFT_RANK_LANES);
+    VFT_SELPH_USE(rank);
+    VFT_SELPH(2, 3);
     if (sub == 0) {
         if (mine && rank < (unsigned int) k) {
             HIT h;
             h.j = myId;
-            h.dist = dist[myId];
-            h.weight = weight[myId];
-            h.criterion = crit[myId];
+            h.dist = myDist;
+            h.weight = myWeight;
+            h.criterion = myCrit;
             vft_hit_publish<HIT>(hits + rank, h);
         }
         if (cand >= n && cand < (unsigned int) k) {   // fewer candidates than requested: empty records
@@ -2832,12 +3022,15 @@ __global__ __launch_bounds__(VFT_WG) void k_select_rank(const SelSlot *slots, in
     __shared__ unsigned int sLast;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wavefront's records have left the chip's caches
     __syncthreads();
+    VFT_SELPH(2, 4);
     if (threadIdx.x == 0) {
         const unsigned int active = (span + perWg - 1) / perWg;
         sLast = __hip_atomic_fetch_add(&S->rankDone, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == active - 1 ? 1u : 0u;
     }
     __syncthreads();
+    VFT_SELPH(2, 5);
     if (!sLast) return;
+    VFT_SELPH(3, 0);
     const int64_t query = sl.query;
     SelectHeader *hdr = sl.hdr, *hostHdr = sl.hostHdr;
     __shared__ long long sBest;
@@ -2847,6 +3040,10 @@ __global__ __launch_bounds__(VFT_WG) void k_select_rank(const SelSlot *slots, in
     for (int t = threadIdx.x; t < VFT_NBINS; t += VFT_WG) sl.slices[t] = 0;
     // The records into the host's block, whole lines per wavefront.  (Measured and dropped in round 6: every workgroup writing its own
     // records there as it ranks them - 2 000 scattered 16-byte writes per seed over PCIe - took the kernel from 40 to 120 us.)
+    // (id, criterion) of record threadIdx.x < 64: what wavefront 0 looks for the best join in - each lane keeps its own pair, in LDS
+    // and not in registers (a record of the double-precision kernel is eight of them)
+    __shared__ long long sHeadJ[64];
+    __shared__ REAL sHeadC[64];
     for (int t0 = 0; t0 < k; t0 += 8 * VFT_WG) {   // (eight records per thread in flight: the fetches are L2 round trips)
         HIT tmp[8];
 #pragma unroll
@@ -2854,13 +3051,60 @@ __global__ __launch_bounds__(VFT_WG) void k_select_rank(const SelSlot *slots, in
             const int t = t0 + u * VFT_WG + (int) threadIdx.x;
             tmp[u] = vft_hit_fetch<HIT>(hits + (t < k ? t : 0));
         }
+        if (t0 == 0 && threadIdx.x < 64) {
+            sHeadJ[threadIdx.x] = (long long) tmp[0].j;
+            sHeadC[threadIdx.x] = tmp[0].criterion;
+        }
 #pragma unroll
         for (int u = 0; u < 8; u++) {
             const int t = t0 + u * VFT_WG + (int) threadIdx.x;
             if (t < k) hostHits[t] = tmp[u];
         }
     }
-    if (threadIdx.x == 0) {
+    VFT_SELPH(3, 1);
+    // bestjoin.  The run of minimal criteria at the head of the list is a few records long: wavefront 0 finds its end among the first 64
+    // records, which it holds, with two ballots - the scan below, one L2 round trip per record by one thread, only when the run (or a
+    // stretch of skipped records) reaches record 64.  Same answer: the query and empty records are skipped, the first other record
+    // sets the minimum (none if it is a sentinel), the run ends at the first other criterion, the smallest id of the run wins.
+    bool serialScan = false;
+    if (threadIdx.x < 64) {
+        const unsigned int nn = n < (unsigned int) k ? n : (unsigned int) k;
+        const long long j = nn ? sHeadJ[threadIdx.x] : -1;   // (nn > 0: k > 0, the copy loop has run)
+        const REAL c = nn ? sHeadC[threadIdx.x] : (REAL) 1e20;
+        const bool counts = threadIdx.x < nn && !(j == query || j < 0);
+        const unsigned long long mCounts = __ballot(counts);
+        long long best = -1;
+        REAL bc = (REAL) 1e20;
+        int truncated = 0;
+        if (mCounts == 0) {
+            serialScan = nn > 64;
+        } else {
+            const REAL c0 = __shfl(c, __ffsll((long long) mCounts) - 1, 64);
+            if (c0 < (REAL) 1e20) {
+                const unsigned long long mEnd = __ballot(counts && !(c == c0));
+                if (mEnd == 0 && nn > 64) {
+                    serialScan = true;
+                } else {
+                    const unsigned int end = mEnd ? (unsigned int) __ffsll((long long) mEnd) - 1 : 64u;
+                    long long mj = counts && threadIdx.x < end ? j : 0x7fffffffffffffffll;
+#pragma unroll
+                    for (int off = 32; off > 0; off >>= 1) {
+                        const long long o = __shfl_xor(mj, off, 64);
+                        mj = o < mj ? o : mj;
+                    }
+                    best = mj;
+                    bc = c0;
+                    truncated = (mEnd == 0 && nn == (unsigned int) k) ? 1 : 0;   // the list ended inside the run: see below
+                }
+            }
+        }
+        if (!serialScan && threadIdx.x == 0) {
+            sBest = best;
+            sCrit = bc;
+            sTruncatedTie = truncated;
+        }
+    }
+    if (serialScan && threadIdx.x == 0) {
         const unsigned int nn = n < (unsigned int) k ? n : (unsigned int) k;
         long long best = -1;
         REAL bc = (REAL) 1e20;
@@ -2887,6 +3131,7 @@ __global__ __launch_bounds__(VFT_WG) void k_select_rank(const SelSlot *slots, in
         sTruncatedTie = (best >= 0 && t == nn && nn == (unsigned int) k) ? 1 : 0;
     }
     __syncthreads();
+    VFT_SELPH(3, 2);
     if (sTruncatedTie) {   // rare: every listed hit ties at the minimum - scan the criteria themselves
         const REAL bc = sCrit;
         long long mineJ = sBest;
@@ -2900,6 +3145,7 @@ __global__ __launch_bounds__(VFT_WG) void k_select_rank(const SelSlot *slots, in
     __threadfence_system();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    VFT_SELPH(3, 3);
     if (threadIdx.x != 0) return;
     SelectHeader h;
     h.nCand = S->nCand;
@@ -2915,6 +3161,8 @@ __global__ __launch_bounds__(VFT_WG) void k_select_rank(const SelSlot *slots, in
     hostHdr->pad = 0;
     hostHdr->bestJ = h.bestJ;
     __hip_atomic_store(&hostHdr->pad2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    VFT_SELPH_DRAIN();
+    VFT_SELPH(3, 4);
 }
 
 // Merge of per-shard hit lists (multi-GPU: each rank's sorted top-k, all-gathered): rank sort of the n = lists * k
