@@ -53,3 +53,9 @@ for si, i in enumerate(starts):
         ops = collections.Counter(x.split()[0] for _, x in ins[j:k + 1] if x.startswith("v_"))
         print("  loop %x..%x: %5d instructions  %s" % (ins[j][0], ins[k][0], k - j + 1, dict(c)))
         print("      VALU by opcode:", ", ".join("%s %d" % p for p in ops.most_common(14)))
+        # memory instructions by opcode, lane traffic and full drains: what tells a pipelined loop from one that waits for every load
+        mem = collections.Counter(x.split()[0] for _, x in ins[j:k + 1] if cls(x) in ("SMEM", "VMEM", "LDS"))
+        lanes = sum(1 for _, x in ins[j:k + 1] if re.match(r"v_(readlane|writelane)", x))
+        waits = collections.Counter(re.sub(r"\s+", " ", x.split(None, 1)[1]) for _, x in ins[j:k + 1] if x.startswith("s_waitcnt") and "vmcnt" in x)
+        print("      memory by opcode:", ", ".join("%s %d" % p for p in mem.most_common(10)) or "-")
+        print("      v_readlane / v_writelane: %d; waits on vmcnt: %s" % (lanes, ", ".join("%s x%d" % p for p in sorted(waits.items())) or "-"))

@@ -2247,6 +2247,19 @@ static int run_select(vft_ctx *c, int K, const int64_t *queries, int64_t lo, int
     return VFT_OK;
 }
 
+#ifdef VFT_SWEEP_WG_CLOCKS   // tools-only build (tools/sweep_wg_clocks.py): never in the product library
+// the workgroup clocks of the last k_sweep_nt_mixed_multi: out[VFT_SWCLK_MAX][3] (tag, entry, exit; 100 MHz ticks); the device copy is zeroed
+extern "C" int vft_debug_sweep_wg_clocks(vft_ctx *c, unsigned long long *out, int64_t nOut) {
+    if (nOut != (int64_t) VFT_SWCLK_MAX * 3) return fail(c, VFT_ERR_INVALID, "vft_debug_sweep_wg_clocks: %d x 3 words", VFT_SWCLK_MAX);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyFromSymbol(out, HIP_SYMBOL(vft_swclk), sizeof(vft_swclk)));
+    void *dev = nullptr;
+    HIPCHK(c, hipGetSymbolAddress(&dev, HIP_SYMBOL(vft_swclk)));
+    HIPCHK(c, hipMemset(dev, 0, sizeof(vft_swclk)));
+    return VFT_OK;
+}
+#endif
+
 #ifdef VFT_SELECT_PHASES   // tools-only build (tools/select_phases.py): never in the product library
 // the phase clocks of the last selection: out[VFT_SELPH_ROWS][VFT_SELPH_SEEDS][VFT_SELPH_MARKS] (100 MHz ticks); the device copy is zeroed
 extern "C" int vft_debug_select_phases(vft_ctx *c, unsigned long long *out, int64_t nOut) {
@@ -2377,7 +2390,13 @@ static bool mixed_sweep_fits(vft_ctx *c) {
     // partial, so slot 0's, one entry shorter, holds twice as many floats as the later slots' bound allows.
     if (c->rs != 4) return false;
     const int64_t N = slot_nodes(c, 1);
+#if VFT_SHARED_LEAF_WALK
+    // (a leaf seed's partials are numbered like a profile seed's: one per leaf span and one per internal workgroup; the shared leaf
+    // walk keeps a (seed, leaf)'s two column counts in the halves of one register: vft_seq_counts_packed)
+    return c->d.nPos < 65536 && (int64_t) grid <= (int64_t) cdiv(N, VFT_WG);
+#else
     return (int64_t) cdiv(s.leafEnd - s.lo, VFT_WG) + (int64_t) (grid - (unsigned) s.nLeafWG) <= (int64_t) cdiv(N, VFT_WG);
+#endif
 }
 
 // a full group of leaf seeds and a full group of profile seeds of a batch in ONE pass over the targets (k_sweep_nt_mixed_multi): results
@@ -2398,12 +2417,17 @@ static int sweep_mixed(vft_ctx *c, const int *leafPos, const int *profPos, const
     s.queryIsLeaf = 0;
     const unsigned gridP = sweep_nt_grid(c, s, true);   // the profile seeds' geometry: nLeafWG table spans + the internal workgroups
     a.nInt = (int32_t) (gridP - (unsigned) s.nLeafWG);
+#if VFT_SHARED_LEAF_WALK
+    const int nPartL = (int) gridP, nLeafWGs = s.nLeafWG;   // the leaves: nLeafWG spans, every seed of both kinds in each
+#else
     a.nLeafHeavy = (int32_t) cdiv(s.leafEnd - s.lo, VFT_WG);
+    const int nPartL = a.nLeafHeavy + a.nInt, nLeafWGs = a.nLeafHeavy + s.nLeafWG;
+#endif
     for (int q = 0; q < S; q++) {
         a.M.L.Q[q] = qbuf_slot<REAL>(c, leafPos[q]);
         a.M.L.O[q] = sweepout<REAL>(c, leafPos[q]);
         a.M.L.query[q] = queries[leafPos[q]];
-        c->slots[(size_t) leafPos[q]].nPart = a.nLeafHeavy + a.nInt;
+        c->slots[(size_t) leafPos[q]].nPart = nPartL;
         a.M.P.Q[q] = qbuf_slot<REAL>(c, profPos[q]);
         a.M.P.O[q] = sweepout<REAL>(c, profPos[q]);
         a.M.P.query[q] = queries[profPos[q]];
@@ -2414,7 +2438,7 @@ static int sweep_mixed(vft_ctx *c, const int *leafPos, const int *profPos, const
     a.M.P.mq = (const REAL *) mq;
     a.M.P.lq = nullptr;
     kernel_event(c);
-    launch((k_sweep_nt_mixed_multi<REAL, S, S>), dim3((unsigned) (a.nInt + a.nLeafHeavy + s.nLeafWG)), dim3(VFT_WG), 0, c->stream, a);
+    launch((k_sweep_nt_mixed_multi<REAL, S, S>), dim3((unsigned) (a.nInt + nLeafWGs)), dim3(VFT_WG), 0, c->stream, a);
     kernel_event(c);
     kernel_event(c);
     if (c->timeKernels) c->kevSweeps += 2 * S - 1;   // (one triple of events, 2 S sweeps)

@@ -229,6 +229,14 @@ __device__ __forceinline__ void vft_seq_counts(const uint4 a, const uint4 b, int
     nSame += __popc(x & 0x0F0F0F0Fu) + __popc(y & 0x0F0F0F0Fu) + __popc(z & 0x0F0F0F0Fu) + __popc(w & 0x0F0F0F0Fu);
 }
 
+// the same counts in one register, nUse in the low half and nSame in the high half (alignments of fewer than 65 536 columns)
+__device__ __forceinline__ void vft_seq_counts_packed(const uint4 a, const uint4 b, uint32_t &cnt) {
+    const uint32_t x = a.x & b.x, y = a.y & b.y, z = a.z & b.z, w = a.w & b.w;
+    const uint32_t same = __popc(x & 0x0F0F0F0Fu) + __popc(y & 0x0F0F0F0Fu) + __popc(z & 0x0F0F0F0Fu) + __popc(w & 0x0F0F0F0Fu);
+    cnt += __popc(x & 0x10101010u) + __popc(y & 0x10101010u) + __popc(z & 0x10101010u) + __popc(w & 0x10101010u);
+    cnt += same << 16;
+}
+
 // Nucleotide, no distance matrix (the -nt default).  NC == 4.
 // ---- internal targets: one 16-column chunk of one tile, as registers of the lane that owns the target.
 // Every column is brought to the "both sides hold a vector" form of profileDistPiece (NJ.tcc:933-937):
@@ -1275,9 +1283,9 @@ __device__ __forceinline__ void vft_int_chunk_consume_shared(const IntChunkAll<f
 // VFT_PTILE_M positions at a time (S x 112 x 5 x 16 B = 35 KB: four workgroups of this kernel still share a CU's LDS), the span's
 // compacted leaves are walked 2 x VFT_WG at a time (two leaves per lane: S x 2 reads in flight per column).
 #define VFT_PTILE_M 112
-template <int NBT, int S>
+template <int NBT, int S, int GCF = 0>
 __device__ __forceinline__ void vft_leaf_table_chunk_multi(const double2 *row, const uint4 *t, double (*top)[S], double (*denom)[S]) {
-    constexpr int GC = NBT * S >= 8 ? 1 : NBT * S >= 4 ? 2 : 4;
+    constexpr int GC = GCF ? GCF : NBT * S >= 8 ? 1 : NBT * S >= 4 ? 2 : 4;
 #pragma unroll
     for (int g = 0; g < VFT_CHUNK; g += GC) {
         double2 v[NBT][GC][S];
@@ -1301,9 +1309,47 @@ __device__ __forceinline__ void vft_leaf_table_chunk_multi(const double2 *row, c
     }
 }
 
-template <typename REAL, int NBT, int S>
+// SL > 0 (vft_leaf_table_wg_mixed): SL LEAF seeds ride on the same walk - behind a chunk's table reads, the popcounts of seqDist
+// (vft_seq_counts_packed) on the chunk the lane already holds, against the seeds' encoded chunks `enc[q][c]`.  Those are wave-uniform and
+// come by scalar loads, one chunk ahead like the leaves' bytes (ping-pong ea / eb: SL x 4 SGPRs each).
+template <int SL>
+struct LeafEncChunk {
+    uint4 e[SL > 0 ? SL : 1];
+};
+template <int SL>
+__device__ __forceinline__ void vft_leaf_enc_load(LeafEncChunk<SL> &d, const uint4 *const *enc, int c) {
+    typedef uint32_t __attribute__((ext_vector_type(4))) u4_t;   // (a vector type: one 16-byte scalar load, vft_uniform_load4)
+    typedef const __attribute__((address_space(4))) u4_t *cp_t;
+#pragma unroll
+    for (int q = 0; q < SL; q++) {
+        const u4_t v = *((cp_t) enc[q] + c);
+        d.e[q] = make_uint4(v.x, v.y, v.z, v.w);
+    }
+}
+// one chunk of the walk: the S tables, then (SL > 0) the SL leaf seeds' counts on the same bytes.  With leaf seeds aboard the two
+// leaves of a lane take their table reads one after the other, S reads in flight instead of 2 S: the 16 registers that frees, the
+// packed counts and the fence in front of them keep the kernel at the 137 registers it had (each (seed, leaf) still adds its columns
+// in order: same bits).
+template <int NBT, int S, int SL>
+__device__ __forceinline__ void vft_leaf_walk_chunk(const double2 *row, const uint4 *t, double (*top)[S], double (*denom)[S],
+                                                    const LeafEncChunk<SL> &e, uint32_t (*cnt)[SL > 0 ? SL : 1]) {
+    if constexpr (SL > 0) {
+#pragma unroll
+        for (int bt = 0; bt < NBT; bt++) vft_leaf_table_chunk_multi<1, S, 1>(row, t + bt, top + bt, denom + bt);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int bt = 0; bt < NBT; bt++)
+#pragma unroll
+            for (int q = 0; q < SL; q++) vft_seq_counts_packed(t[bt], e.e[q], cnt[bt][q]);
+    } else {
+        vft_leaf_table_chunk_multi<NBT, S>(row, t, top, denom);
+    }
+}
+
+template <typename REAL, int NBT, int S, int SL = 0>
 __device__ __forceinline__ void vft_leaf_table_walk_multi(const Arena<REAL> &A, const MultiLeafQ<REAL, S> &M, double2 *tab, const int64_t *tj,
-                                                          double (*top)[S], double (*denom)[S]) {
+                                                          double (*top)[S], double (*denom)[S], const uint4 *const *enc = nullptr,
+                                                          uint32_t (*cnt)[SL > 0 ? SL : 1] = nullptr) {
     const int tid = threadIdx.x;
     const int64_t nPos = A.d.nPos;
     const uint4 *lp[NBT];
@@ -1322,18 +1368,22 @@ __device__ __forceinline__ void vft_leaf_table_walk_multi(const Arena<REAL> &A, 
         const int c0 = (int) (p0 / VFT_CHUNK);
         const int c1 = (int) (((p0 + VFT_PTILE_M < nPos ? p0 + VFT_PTILE_M : nPos) + VFT_CHUNK - 1) / VFT_CHUNK);
         uint4 ta[NBT], tb[NBT];   // the leaves' bytes one chunk ahead, ping-pong (vft_leaf_table_walk)
+        LeafEncChunk<SL> ea, eb;  // the leaf seeds' chunks likewise (scalar registers)
 #pragma unroll
         for (int bt = 0; bt < NBT; bt++) ta[bt] = lp[bt][(int64_t) c0 * VFT_TILE];
+        if constexpr (SL > 0) vft_leaf_enc_load<SL>(ea, enc, c0);
         for (int c = c0; c < c1; c += 2) {
             const int cb = c + 1 < c1 ? c + 1 : c, ca = c + 2 < c1 ? c + 2 : c;
 #pragma unroll
             for (int bt = 0; bt < NBT; bt++) tb[bt] = lp[bt][(int64_t) cb * VFT_TILE];
+            if constexpr (SL > 0) vft_leaf_enc_load<SL>(eb, enc, cb);
             __builtin_amdgcn_sched_barrier(0);
-            vft_leaf_table_chunk_multi<NBT, S>(tab + (int64_t) (c - c0) * VFT_CHUNK * 5, ta, top, denom);
+            vft_leaf_walk_chunk<NBT, S, SL>(tab + (int64_t) (c - c0) * VFT_CHUNK * 5, ta, top, denom, ea, cnt);
 #pragma unroll
             for (int bt = 0; bt < NBT; bt++) ta[bt] = lp[bt][(int64_t) ca * VFT_TILE];
+            if constexpr (SL > 0) vft_leaf_enc_load<SL>(ea, enc, ca);
             __builtin_amdgcn_sched_barrier(0);
-            if (c + 1 < c1) vft_leaf_table_chunk_multi<NBT, S>(tab + (int64_t) (c + 1 - c0) * VFT_CHUNK * 5, tb, top, denom);
+            if (c + 1 < c1) vft_leaf_walk_chunk<NBT, S, SL>(tab + (int64_t) (c + 1 - c0) * VFT_CHUNK * 5, tb, top, denom, eb, cnt);
         }
     }
 }
@@ -1473,6 +1523,118 @@ __device__ __forceinline__ void vft_block_minmax_karg(REAL *cmin, REAL *cmax, co
     }
 }
 
+// -DVFT_NO_SHARED_LEAF_WALK (a variant build, for A/B runs) compiles vft_leaf_table_wg_mixed out: k_sweep_nt_mixed_multi walks the leaf
+// targets twice as before - a leaf per lane for the leaf seeds, the table workgroups for the profile seeds.
+#ifdef VFT_NO_SHARED_LEAF_WALK
+#define VFT_SHARED_LEAF_WALK 0
+#else
+#define VFT_SHARED_LEAF_WALK 1
+#endif
+#if VFT_SHARED_LEAF_WALK
+// ---- a span's leaves against SP profile seeds AND SL leaf seeds in one walk (k_sweep_nt_mixed_multi): vft_leaf_table_wg_multi's
+// compaction and walk for the profile seeds `P`, with the leaf seeds' popcounts (k_sweep_nt_leafq_multi's leaf targets) on the chunks
+// the walk holds - a leaf's bytes, parent, out-distance and sentinel decision once for all SL + SP seeds.  Per (seed, leaf) the
+// operations of the two walks it replaces, on the same operands: same bits.  The leaf seeds' buffers are read through vft_kernarg
+// (offset offL of the argument block) where they are used: nothing of them lives across the walk but the SL pointers to their
+// encoded chunks.
+template <typename REAL, int SL, int SP>
+__device__ __forceinline__ void vft_leaf_table_wg_mixed(const Arena<REAL> &A, const MultiLeafQ<REAL, SP> &P, size_t offL, const SweepArgs &s,
+                                                        int64_t base, REAL *cminP, REAL *cmaxP, REAL *cminL, REAL *cmaxL) {
+    constexpr int NB = VFT_LEAF_SPAN / VFT_WG, NW = VFT_WG / 64, NBT = 2;
+    __shared__ double2 tab[SP * VFT_PTILE_M * 5];
+    __shared__ unsigned short list[VFT_LEAF_SPAN];
+    __shared__ int segCnt[NB * NW];
+    const int tid = threadIdx.x, wave = tid >> 6;
+    // 1. compaction of the span's active leaves (order-preserving); the others get the "illegal join" sentinel of every seed
+    // (vft_kernarg's asm wants uniform control flow: the pointer is made outside the per-lane branches)
+    const VFT_KARG MultiLeafQ<REAL, SL> *L0 = vft_kernarg<MultiLeafQ<REAL, SL>>(offL);
+    unsigned long long bal[NB];
+#pragma unroll
+    for (int r = 0; r < NB; r++) {
+        const int64_t j = base + r * VFT_WG + tid;
+        bool active = false;
+        if (j < s.leafEnd) {
+            active = A.parent[j] < 0;
+            if (!active) {
+#pragma unroll
+                for (int q = 0; q < SP; q++) {
+                    P.O[q].dist[j] = (REAL) 1e20;
+                    P.O[q].crit[j] = (REAL) 1e20;
+                    P.O[q].weight[j] = 0;
+                }
+                vft_karg_sentinels<REAL, SL>(L0, j);
+            }
+        }
+        bal[r] = __ballot(active);
+        if ((tid & 63) == 0) segCnt[r * NW + wave] = __popcll(bal[r]);
+    }
+    __syncthreads();
+    int nAct = 0, off[NB];
+#pragma unroll
+    for (int seg = 0; seg < NB * NW; seg++) {
+#pragma unroll
+        for (int r = 0; r < NB; r++)
+            if (seg == r * NW + wave) off[r] = nAct;
+        nAct += segCnt[seg];
+    }
+#pragma unroll
+    for (int r = 0; r < NB; r++) {
+        const int rank = (int) __builtin_amdgcn_mbcnt_hi((unsigned int) (bal[r] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int) bal[r], 0u));
+        if ((bal[r] >> (tid & 63)) & 1ull) list[off[r] + rank] = (unsigned short) (r * VFT_WG + tid);
+    }
+    __syncthreads();
+    // 2. two leaves per lane at a time
+    for (int r0 = 0; r0 < nAct; r0 += NBT * VFT_WG) {   // workgroup-uniform
+        int64_t tj[NBT];
+        double top[NBT][SP], denom[NBT][SP];
+        uint32_t cnt[NBT][SL];   // nUse | nSame << 16 (vft_seq_counts_packed)
+#pragma unroll
+        for (int bt = 0; bt < NBT; bt++) {
+            const int idx = r0 + bt * VFT_WG + tid;
+            tj[bt] = base + list[idx < nAct ? idx : 0];   // lanes beyond the list redo entry 0 and drop the result
+#pragma unroll
+            for (int q = 0; q < SP; q++) top[bt][q] = denom[bt][q] = 0;
+#pragma unroll
+            for (int q = 0; q < SL; q++) cnt[bt][q] = 0;
+        }
+        {
+            const VFT_KARG MultiLeafQ<REAL, SL> *L1 = vft_kernarg<MultiLeafQ<REAL, SL>>(offL);
+            const uint4 *enc[SL];
+#pragma unroll
+            for (int q = 0; q < SL; q++) enc[q] = L1->Q[q].enc;
+            if (nAct - r0 <= VFT_WG) vft_leaf_table_walk_multi<REAL, 1, SP, SL>(A, P, tab, tj, top, denom, enc, cnt);
+            else vft_leaf_table_walk_multi<REAL, NBT, SP, SL>(A, P, tab, tj, top, denom, enc, cnt);
+        }
+        const VFT_KARG MultiLeafQ<REAL, SL> *Lk = vft_kernarg<MultiLeafQ<REAL, SL>>(offL);   // after the walk: the epilogue's
+#pragma unroll
+        for (int bt = 0; bt < NBT; bt++) {
+            const int idx = r0 + bt * VFT_WG + tid;
+            tj[bt] = base + list[idx < nAct ? idx : 0];   // (read again: not held across the walk)
+            if (idx < nAct) {
+#pragma unroll
+                for (int q = 0; q < SP; q++) {
+                    const REAL weight = (REAL) (denom[bt][q] > 0 ? denom[bt][q] : 0.01);
+                    const REAL dist = (REAL) (denom[bt][q] > 0 ? top[bt][q] / denom[bt][q] : 1.0);
+                    SweepArgs sq = s;
+                    sq.query = P.query[q];
+                    vft_sweep_finish<REAL, MODE_CRIT>(A, sq, P.O[q], tj[bt], dist, weight, false, cminP[q], cmaxP[q]);
+                }
+#pragma unroll
+                for (int q = 0; q < SL; q++) {   // seqDist from the counts (NJ.tcc:1601-1612), as k_sweep_nt_leafq_multi
+                    const int nUse = (int) (cnt[bt][q] & 0xFFFFu), nSame = (int) (cnt[bt][q] >> 16);
+                    const double topq = (double) (nUse - nSame);
+                    const REAL weight = (REAL) (double) nUse;
+                    const REAL dist = (REAL) (nUse > 0 ? topq / (double) nUse : 1.0);
+                    SweepArgs sq = s;
+                    sq.query = Lk->query[q];
+                    vft_sweep_finish<REAL, MODE_CRIT>(A, sq, vft_karg_out<REAL>(&Lk->O[q]), tj[bt], dist, weight, true, cminL[q], cmaxL[q]);
+                }
+            }
+        }
+    }
+}
+#endif
+
 // (three wavefronts per SIMD in single precision: at four - 128 VGPRs - 23 registers of the column loop went to scratch, nine scratch
 // accesses per 16-column chunk and 120 MB of extra write traffic per launch (rocprofv3 WRITE_SIZE 181 MB against 60 MB of results);
 // with 137 registers nothing spills: 240 -> 215 us per launch of four profile seeds)
@@ -1542,11 +1704,13 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
 // VFT_SHARED_PIECES a group's profile seeds first, vft_int_chunk_consume_prof, then its leaf seeds, vft_int_chunk_consume_all); per
 // (seed, target) the operations are those of the per-kind kernels, in their order: same bits.  Workgroups, in launch order:
 //   1. nInt "internal" ones over [s.heavyLo, s.hi), highest ids first, ids >= s.leafEnd only: all SL + SP seeds
-//   2. nLeafHeavy over [s.lo, s.leafEnd), a leaf per lane: the leaf seeds' popcount distances (k_sweep_nt_leafq_multi's leaf targets)
-//   3. s.nLeafWG table workgroups over the same leaves: the profile seeds (vft_leaf_table_wg_multi)
-// Every (seed, target) buffer entry belongs to exactly one workgroup.  Min / max partials: a profile seed's are numbered as in
-// k_sweep_nt_profq_multi (span, nLeafWG + wg: nLeafWG + nInt of them), a leaf seed's [leaf-range workgroup, nLeafHeavy + wg]
-// (nLeafHeavy + nInt) - each seed's range is written completely, by workgroups that serve it.
+//   2. s.nLeafWG leaf workgroups over [s.lo, s.leafEnd), VFT_LEAF_SPAN ids each, highest spans first: all SL + SP seeds in one walk
+//      over the span's compacted leaves (vft_leaf_table_wg_mixed) - the profile seeds' tables and the leaf seeds' popcounts
+// Every (seed, target) buffer entry belongs to exactly one workgroup.  Min / max partials of all SL + SP seeds are numbered as in
+// k_sweep_nt_profq_multi: span, nLeafWG + wg (nLeafWG + nInt of them).
+// (-DVFT_NO_SHARED_LEAF_WALK, and every build before the shared walk: 2. nLeafHeavy workgroups over the leaves, a leaf per lane, for the
+// leaf seeds' popcount distances, then 3. the table workgroups, lowest spans first, for the profile seeds (vft_leaf_table_wg_multi);
+// a leaf seed's partials [leaf-range workgroup, nLeafHeavy + wg].)
 //
 // The seeds' buffers and ids (2 x MultiLeafQ) are needed before the column loop (sentinels) and after it (epilogue), the loop itself
 // wants one pointer for the profile seeds (mq) and one for the leaf seeds (lq, their code record).  Passed as a plain kernel argument the compiler loads
@@ -1562,9 +1726,33 @@ template <typename REAL, int SL, int SP>
 struct MixedArgs {   // the kernel's only argument: the offset of M in the kernel-argument segment is offsetof(MixedArgs, M)
     Arena<REAL> A;
     SweepArgs s;     // the PROFILE seeds' geometry (sweep_nt_grid with the table path): lo, hi, leafEnd, heavyLo, nLeafWG
+#if VFT_SHARED_LEAF_WALK
+    int32_t nInt, pad;
+#else
     int32_t nInt, nLeafHeavy;
+#endif
     MixedQ<REAL, SL, SP> M;
 };
+// Workgroup clocks of k_sweep_nt_mixed_multi (tools/sweep_wg_clocks.py) exist only in builds made with -DVFT_SWEEP_WG_CLOCKS (a variant
+// build, veryfasttree_amd/build.py); in the product build the marks are nothing.  Thread 0 of every workgroup stores, with ordinary
+// vector stores, [kind | 16 x "a target of the workgroup was active"], wall_clock64() (100 MHz) at entry and at exit.
+#ifdef VFT_SWEEP_WG_CLOCKS
+#define VFT_SWCLK_MAX 8192   // workgroups recorded (the headline grid: 1 954, or 5 861 without the shared leaf walk)
+__device__ unsigned long long vft_swclk[VFT_SWCLK_MAX][3];
+#define VFT_SWCLK_BEGIN() const unsigned long long vft_swclk_t0 = wall_clock64()
+#define VFT_SWCLK_END(kind, worked)                                                                                    \
+    do {                                                                                                               \
+        const int vft_swclk_any = __syncthreads_or((int) (worked));                                                    \
+        if (threadIdx.x == 0 && blockIdx.x < VFT_SWCLK_MAX) {                                                          \
+            vft_swclk[blockIdx.x][0] = (unsigned long long) ((kind) | (vft_swclk_any ? 16 : 0));                       \
+            vft_swclk[blockIdx.x][1] = vft_swclk_t0;                                                                   \
+            vft_swclk[blockIdx.x][2] = wall_clock64();                                                                 \
+        }                                                                                                              \
+    } while (0)
+#else
+#define VFT_SWCLK_BEGIN() ((void) 0)
+#define VFT_SWCLK_END(kind, worked) ((void) 0)
+#endif
 template <typename REAL, int SL, int SP>
 __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_mixed_multi(MixedArgs<REAL, SL, SP> a) {
     typedef MixedArgs<REAL, SL, SP> Args;
@@ -1573,7 +1761,12 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
     __shared__ REAL smin[SL + SP][NW], smax[SL + SP][NW];
     const Arena<REAL> &A = a.A;
     const SweepArgs &s = a.s;
+#if VFT_SHARED_LEAF_WALK
+    const int blk = (int) blockIdx.x, nInt = a.nInt, nT = s.nLeafWG;
+#else
     const int blk = (int) blockIdx.x, nInt = a.nInt, nLH = a.nLeafHeavy, nT = s.nLeafWG;
+#endif
+    VFT_SWCLK_BEGIN();
     REAL cminP[SP], cmaxP[SP], cminL[SL], cmaxL[SL];
 #pragma unroll
     for (int q = 0; q < SP; q++) {
@@ -1585,8 +1778,13 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
         cminL[q] = (REAL) 1e30;
         cmaxL[q] = (REAL) -1e30;
     }
+#if VFT_SHARED_LEAF_WALK
+    if (blk >= nInt) {   // 2. a leaf workgroup: span `span` of the leaves against all seeds, highest spans first
+        const int span = nT - 1 - (blk - nInt);
+#else
     if (blk >= nInt + nLH) {   // 3. a table workgroup: span `span` of the leaves against the profile seeds
         const int span = blk - nInt - nLH;
+#endif
         const VFT_KARG MultiLeafQ<REAL, SP> *Pk = vft_kernarg<MultiLeafQ<REAL, SP>>(offP);
         MultiLeafQ<REAL, SP> M;
 #pragma unroll
@@ -1600,8 +1798,17 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
             M.query[q] = Pk->query[q];
         }
         M.mq = Pk->mq;
+#if VFT_SHARED_LEAF_WALK
+        vft_leaf_table_wg_mixed<REAL, SL, SP>(A, M, offL, s, s.lo + (int64_t) span * VFT_LEAF_SPAN, cminP, cmaxP, cminL, cmaxL);
+        vft_block_minmax_karg<REAL, SP>(cminP, cmaxP, vft_kernarg<MultiLeafQ<REAL, SP>>(offP), span, smin, smax);
+        vft_block_minmax_karg<REAL, SL>(cminL, cmaxL, vft_kernarg<MultiLeafQ<REAL, SL>>(offL), span, smin + SP, smax + SP);
+        VFT_SWCLK_END(4, cminP[0] < (REAL) 1e30);
+        return;
+    }
+#else
         vft_leaf_table_wg_multi<REAL, SP>(A, M, s, s.lo + (int64_t) span * VFT_LEAF_SPAN, cminP, cmaxP);
         vft_block_minmax_karg<REAL, SP>(cminP, cmaxP, vft_kernarg<MultiLeafQ<REAL, SP>>(offP), span, smin, smax);
+        VFT_SWCLK_END(3, cminP[0] < (REAL) 1e30);
         return;
     }
     if (blk >= nInt) {   // 2. leaves against the leaf seeds: encoded bytes, integer counts (seqDist, NJ.tcc:1601-1612)
@@ -1640,8 +1847,10 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
             }
         }
         vft_block_minmax_karg<REAL, SL>(cminL, cmaxL, vft_kernarg<MultiLeafQ<REAL, SL>>(offL), wg, smin, smax);
+        VFT_SWCLK_END(2, cminL[0] < (REAL) 1e30);
         return;
     }
+#endif
     // 1. internal targets against all seeds
     const int wg = nInt - 1 - blk;   // highest ids first, as in k_sweep_nt
     const int64_t j = s.heavyLo + (int64_t) wg * VFT_WG + threadIdx.x;
@@ -1711,7 +1920,12 @@ __global__ __launch_bounds__(VFT_WG, sizeof(REAL) == 4 ? 3 : 2) void k_sweep_nt_
         }
     }
     vft_block_minmax_karg<REAL, SP>(cminP, cmaxP, vft_kernarg<MultiLeafQ<REAL, SP>>(offP), nT + wg, smin, smax);
+#if VFT_SHARED_LEAF_WALK
+    vft_block_minmax_karg<REAL, SL>(cminL, cmaxL, vft_kernarg<MultiLeafQ<REAL, SL>>(offL), nT + wg, smin + SP, smax + SP);
+#else
     vft_block_minmax_karg<REAL, SL>(cminL, cmaxL, vft_kernarg<MultiLeafQ<REAL, SL>>(offL), nLH + wg, smin + SP, smax + SP);
+#endif
+    VFT_SWCLK_END(1, cminP[0] < (REAL) 1e30);
 }
 
 // ------------------------------------------------------------------------------------------------ generic pair
