@@ -265,6 +265,17 @@ int vft_nj_round_plan(int64_t n_seqs, int32_t nni_rounds, int32_t ml_nni_rounds,
    alpha, the factor every branch length was multiplied by (the reference's "Gamma(20) LogLk = .. alpha = .. rescaling lengths by ..") */
 int vft_nj_last_gamma(double *out);
 
+/* `-log FILE`: the descriptor to which the following vft_nj_newick / vft_nj_ml_newick of this process write the reference's log lines
+   (host/StageLog.h), each with write(2) as its stage finishes - a run that fails leaves the lines of the stages it
+   completed.  fd < 0 switches logging off, which is the default; the descriptor stays the caller's (it is never closed here).  The
+   first line, `# veryfasttree-amd log: ...`, says what is written and what is not; vft_nj_make_matrix writes that line alone.  With a
+   vft_comm of several ranks only rank 0 writes.  A write(2) error ends the run with a message that names the log.  With logging off
+   nothing is formatted, no branch length is downloaded and no split is counted that a run without a log would not need.  Process
+   state and not a member of vft_nj_options, as vft_set_approx_ml is state of the context. */
+int vft_nj_set_log(int32_t fd);
+/* the descriptor in force, -1 = logging is off (as vft_get_approx_ml returns its switch) */
+int vft_nj_get_log(void);
+
 /* `-makematrix` (VeryFastTreeImpl.tcc:67-73 -> printDistances, NJ.tcc:274-288): writes to the file descriptor fd what the reference
    prints - per sequence its name, " %f" of the distance to every sequence in input order (the diagonal included), a newline; no
    header.  ctx: a context of `precision` with the n_seqs sequences of the WHOLE alignment uploaded (vft_upload_leaves; the mode does not

@@ -12,6 +12,7 @@ or - with -mllen - the tree of `VeryFastTree -nt -nome -mllen [-nocat | -cat N] 
     python tools/nj_tree.py in.fasta -full -spr 4 -mlacc 2 -slownni [-nni N] [-mlnni N] [-sprlength N] > tree.nwk   # the thorough search
     python tools/nj_tree.py in.fasta -aa [-wag | -lg] -full|-mllen -approxml > tree.nwk   # `VeryFastTree ... -approxml` (alias -mlapprox)
     python tools/nj_tree.py -makematrix [-rawdist] [-aa] [-double] in.fasta > matrix.txt   # `VeryFastTree [-nt] [-rawdist] [-double-precision] -makematrix`
+    python tools/nj_tree.py in.fasta [any mode above] -log FILE > tree.nwk   # `VeryFastTree ... -log FILE`: stage trees, likelihoods, rates
 
 Neighbour joining with top hits on the device (veryfasttree_amd/host/NJDriver.h), the root, minimum-evolution branch
 lengths (updateBranchLengths), local-bootstrap supports (1000 resamples, reliabilityNJ) and printNJ; -nj-lengths keeps
@@ -41,6 +42,9 @@ they end the program with a message.
 -approxml (or -mlapprox): the reference's option of that name - the posteriors of a protein run's ML stages skip the rotation where one
 state dominates and the rest follows the model's near-constant table (NJ.tcc:2390-2421).  Accepted and without effect for nucleotides
 and where no ML stage runs, as in the reference.
+-log FILE: the reference's `-log FILE` - the tree after every stage (NJ, ME_NNI<k>, ME_SPR<k>, ME_Lengths, ML_Lengths<k>, ML_NNI<k>), the TreeLogLk
+lines, the GTR and rate-category lines, with -gamma the per-site Gamma20 table, the clock lines and the summary; the first line says what the
+reference logs and this backend does not (README "-log").  Each line is written when its stage ends.  With -makematrix: that first line alone.
 -boot N: N resamples instead of 1000 for the supports, local (default mode) and SH-like (-mllen, -full) alike, as the reference's
 -boot; -boot 0 is -nosupport.  Local supports take every alignment the NJ phase takes (10 240 columns).
 -full, -mllen, -double, -aa / -jtt and -nj-lengths are this tool's own words; every other flag is the reference's and means what
@@ -52,8 +56,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from veryfasttree_amd import HipProfileOps
-from veryfasttree_amd.backend import make_matrix, nj_newick, VftError
-from veryfasttree_amd.refflags import from_reference_flags
+from veryfasttree_amd.backend import logging_to, make_matrix, nj_newick, VftError
+from veryfasttree_amd.refflags import file_of, from_reference_flags
 from veryfasttree_amd.synth import ALPHABET_AA, ALPHABET_NT, NOCODE
 
 
@@ -99,15 +103,15 @@ def translate(args):
     if "-slow" in args and full:
         sys.exit("-slow with -full is not built: use -slow alone (the tree of -slow -noml -nome) or with -mllen")
     intree = None
-    if "-intree" in args:
+    try:
+        args, start = file_of(args, "-intree")
+    except ValueError as e:
+        sys.exit(str(e))
+    if start is not None:
         if "-slow" in args:
             sys.exit("-intree with -slow is not built")
-        k = args.index("-intree")
-        if k + 1 >= len(args):
-            sys.exit("-intree needs a file")
-        with open(args[k + 1]) as fh:
+        with open(start) as fh:
             intree = fh.read()
-        del args[k:k + 2]
     protein = any(a in args for a in ("-aa", "-jtt", "-wag", "-lg"))
     ref = [] if protein else ["-nt"]
     ref += ["-nome", "-mllen"] if mllen else [] if full else ["-noml", "-nome"]
@@ -121,8 +125,9 @@ def translate(args):
     for flag in NEEDS_FULL:
         if flag in args and not (full or (flag == "-mlacc" and mllen)):
             sys.exit("%s needs -full%s: without it the stage the option belongs to does not run" % (flag, " or -mllen" if flag == "-mlacc" else ""))
-    if run.other:
-        sys.exit("not built in this tool: -%s" % ", -".join(run.other))
+    unbuilt = [key for key in run.other if key != "log"]
+    if unbuilt:
+        sys.exit("not built in this tool: -%s" % ", -".join(unbuilt))
     nj_len = "-nj-lengths" in args
     return path, run._replace(n_bootstrap=0 if nj_len else run.n_bootstrap), nj_len
 
@@ -132,6 +137,10 @@ MAKEMATRIX_FLAGS = ("-makematrix", "-rawdist", "-aa", "-double")
 
 def main_makematrix(args):
     """`-makematrix`: every sequence of the alignment, in input order, against every sequence"""
+    try:
+        args, log = file_of(args, "-log")   # (the log of a -makematrix run is its first line)
+    except ValueError as e:
+        sys.exit(str(e))
     other = [a for a in args if a.startswith("-") and a not in MAKEMATRIX_FLAGS]
     if other:
         sys.exit("-makematrix prints distances and builds no tree: it cannot be combined with %s (allowed: -rawdist, -aa, -double)" % " ".join(other))
@@ -145,7 +154,8 @@ def main_makematrix(args):
     _, codes_all = codes_of(seqs, aa)
     sys.stdout.flush()
     try:   # the text goes to standard output, as the reference's does even with -out
-        make_matrix(codes_all, names, 20 if aa else 4, np.float64 if "-double" in args else np.float32, "-rawdist" in args, 1)
+        with logging_to(log):
+            make_matrix(codes_all, names, 20 if aa else 4, np.float64 if "-double" in args else np.float32, "-rawdist" in args, 1)
     except VftError as e:
         sys.exit(str(e))
 
@@ -172,9 +182,13 @@ def main():
         sys.exit("fewer than 3 unique sequences")
     try:
         tree, loglk = nj_newick(lambda n, L: HipProfileOps(n, L, run.n_codes, run.dtype, max_nodes=3 * n), codes_all, names, me_lengths=not nj_len,
-                                unique=(np.array(unique_first, np.int64), aln_next), n_bootstrap=run.n_bootstrap, return_loglk=True, **run.kwargs)
+                                unique=(np.array(unique_first, np.int64), aln_next), n_bootstrap=run.n_bootstrap, return_loglk=True, log=run.other.get("log"), **run.kwargs)
+    except OSError as e:
+        if run.other.get("log") is None or e.filename != run.other["log"]:   # (only the log's own file is opened on the way)
+            raise
+        sys.exit("-log %s: %s" % (e.filename, e.strerror))
     except VftError as e:
-        if "intree" not in run.kwargs:
+        if "intree" not in run.kwargs and "-log" not in str(e):
             raise
         sys.exit(str(e))
     label = "Round" if "ml_nni" in run.kwargs else "Length"   # of the TreeLogLk lines: by the stages that run, whatever -mlacc adds to a -mllen run

@@ -4,7 +4,9 @@ There is no CPU fallback: if the shared library is missing or no HIP device is p
 Method names follow the reference members they replace (src/NeighbourJoining.tcc), so that the parity tests read
 like calls into the reference.
 """
+import contextlib
 import ctypes as C
+import operator
 import os
 import sys
 
@@ -54,7 +56,7 @@ HIT_F32 = np.dtype([("j", np.int32), ("dist", np.float32), ("weight", np.float32
 HIT_F64 = np.dtype([("j", np.int64), ("dist", np.float64), ("weight", np.float64), ("criterion", np.float64)])
 
 HOST_LIB_PATH = os.path.join(LIB_DIR, "libvft_host.so")
-HOST_EXPORTS = ["vft_nj_run", "vft_nj_newick", "vft_nj_ml_newick", "vft_nj_last_join_crcs", "vft_nj_last_stage_seconds", "vft_nj_last_walk_dual", "vft_nj_last_lane_exchange", "vft_nj_lane_share", "vft_nj_out_profile_block", "vft_nj_last_gamma", "vft_nj_round_plan", "vft_nj_make_matrix", "vft_tree_partitioning", "vft_knuth_stream", "vft_ml_lengths", "vft_gtr_tables",
+HOST_EXPORTS = ["vft_nj_run", "vft_nj_newick", "vft_nj_ml_newick", "vft_nj_last_join_crcs", "vft_nj_last_stage_seconds", "vft_nj_last_walk_dual", "vft_nj_last_lane_exchange", "vft_nj_lane_share", "vft_nj_out_profile_block", "vft_nj_last_gamma", "vft_nj_round_plan", "vft_nj_make_matrix", "vft_nj_set_log", "vft_nj_get_log", "vft_tree_partitioning", "vft_knuth_stream", "vft_ml_lengths", "vft_gtr_tables",
                 "vft_aa_model_tables", "vft_aa_near_tables", "vft_blosum45_tables", "vft_aa_model_as_distance_tables"]
 
 
@@ -290,11 +292,43 @@ def uniquify(codes):
     return np.array(unique_first, np.int64), aln_next
 
 
+def set_log(fd):
+    """vft_nj_set_log: the descriptor the following tree runs of this process write the log to; a negative one (or None) = no log"""
+    load_host_library().vft_nj_set_log(I32(-1 if fd is None or int(fd) < 0 else int(fd)))
+
+
+def get_log():
+    """vft_nj_get_log: the descriptor in force, -1 = logging is off"""
+    return int(load_host_library().vft_nj_get_log())
+
+
+@contextlib.contextmanager
+def logging_to(log):
+    """`-log`: for the block, tree runs write the reference's log lines to `log` - a path (created or truncated, closed behind the
+    block) or an open descriptor (left open); None = no log.  Logging is off again behind the block, also after an error."""
+    if log is None:
+        yield
+        return
+    try:
+        fd, own = operator.index(log), False          # any integer type is a descriptor
+    except TypeError:
+        fd, own = os.open(os.fspath(log), os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644), True
+    try:
+        set_log(fd)
+        yield
+    finally:
+        set_log(-1)
+        if own:
+            os.close(fd)
+
+
 def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtype=np.float32, me_lengths=False,
               unique=None, scoredist=False, n_bootstrap=0, mllen=0, return_loglk=False, return_rates=False, me_nni=False, ml_nni=0, spr=0, gtr=False, return_gtr=False,
               aa_model=None, comm=None, threads=1, debug_flags=0, gamma=False, out_profile_parts=0, slow=False, intree=None, pseudo=0.0,
-              ml_accuracy=1, slow_nni=False, nni_rounds=None, ml_nni_rounds=None, spr_length=None, approx_ml=False):
+              ml_accuracy=1, slow_nni=False, nni_rounds=None, ml_nni_rounds=None, spr_length=None, approx_ml=False, log=None):
     """The NJ phase of the whole alignment `codes_all` (duplicates included) as the reference's "NJ" tree string.
+    log (path or open descriptor): `-log FILE` - the reference's log lines of this run, written as its stages finish (vft_nj_set_log;
+    README "-log"); a path is created or truncated.  None = no log, and nothing is recorded.
     approx_ml: `-approxml` - the ML stages' posteriors of a protein run take the near-constant approximation where it holds; no member
     of vft_nj_options but state of the context: ops.set_approx_ml(True) on what make_ops returns, before the driver runs.
     intree (str): `-intree` - Newick text of a starting tree; the NJ phase does not run (vft_nj_options.intree).
@@ -332,10 +366,11 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
     n_rates = I32(0)
     ratecat = np.zeros(L, np.int32)
     gtr_out = np.zeros(10, np.float64)
-    rc = lib.vft_nj_ml_newick(ops.ctx, _ptr(codes), I64(n), I64(L), I32(np.dtype(dtype).itemsize), C.byref(opt),
-                              I32(1 if me_lengths else 0), I32(n_bootstrap), _ptr(unique_first), _ptr(aln_next),
-                              I64(len(codes_all)), blob, out, I64(cap), C.byref(olen), _ptr(loglk), I32(64),
-                              C.byref(n_rounds), _ptr(rates), I32(64), C.byref(n_rates), _ptr(ratecat), _ptr(gtr_out), err, I32(512))
+    with logging_to(log):
+        rc = lib.vft_nj_ml_newick(ops.ctx, _ptr(codes), I64(n), I64(L), I32(np.dtype(dtype).itemsize), C.byref(opt),
+                                  I32(1 if me_lengths else 0), I32(n_bootstrap), _ptr(unique_first), _ptr(aln_next),
+                                  I64(len(codes_all)), blob, out, I64(cap), C.byref(olen), _ptr(loglk), I32(64),
+                                  C.byref(n_rounds), _ptr(rates), I32(64), C.byref(n_rates), _ptr(ratecat), _ptr(gtr_out), err, I32(512))
     if rc != 0:
         raise VftError(err.value.decode() or "vft_nj_ml_newick failed")
     if return_gtr:

@@ -27,6 +27,7 @@
 #include "../../include/vft_host.h"
 #include "GtrModel.h"
 #include "PseudoDistances.h"
+#include "StageLog.h"
 
 namespace veryfasttree {
 
@@ -307,6 +308,8 @@ namespace veryfasttree {
            site likelihoods with every site at each rate in turn; every site takes the rate with the best likelihood x
            Gamma(3, 1/3) prior; the rates are rescaled to mean 1 over the sites; the profiles are rebuilt.
            rates / ratecat receive the result (what the reference logs as "Rates" / "SiteCategories"). */
+        double avgRate = 1.0;   /* what the last setMLRates divided the categories' rates by (the log's "Rate categories were divided by") */
+
         void setMLRates(int32_t nCat, int64_t nPos, std::vector<REAL> &rates, std::vector<int64_t> &ratecat) {
             ratecat.assign((size_t) nPos, 0);
             if (nCat <= 1) {
@@ -340,7 +343,7 @@ namespace veryfasttree {
                 ratecat[(size_t) p] = best;
                 sumRates += (double) rates[(size_t) best];
             }
-            const double avgRate = sumRates / (double) nPos;
+            avgRate = sumRates / (double) nPos;
             for (int32_t i = 0; i < nCat; i++) rates[(size_t) i] = (REAL) ((double) rates[(size_t) i] / avgRate);
             chk(vft_set_rates(ctx, rates.data(), nCat, ratecat.data()));
             recomputeMLProfiles();
@@ -413,7 +416,7 @@ namespace veryfasttree {
         static double pGamma(double x, double alpha) { return incompleteGamma(x * alpha, alpha, lnGamma(alpha)); }   /* NJ.tcc:5362-5365 */
 
         GammaFit branchlengthScale(int32_t nCat, int64_t nPos, const std::vector<REAL> &curRates, const std::vector<int64_t> &curRatecat,
-                                   const int64_t *gapsPerPos) {
+                                   const int64_t *gapsPerPos, StageLog *log = nullptr) {
             std::vector<REAL> rates((size_t) nCat);
             const double logNCat = std::log((double) nCat);
             const double logd = (logNCat + logNCat) / (double) (nCat - 1);
@@ -471,9 +474,23 @@ namespace veryfasttree {
                 if (fx > start - 0.001) break;
             }
             GammaFit g;
-            g.loglk = gammaLogLk(nullptr);
+            std::vector<double> gammaSites(log ? (size_t) nPos : 0);
+            g.loglk = gammaLogLk(log ? gammaSites.data() : nullptr);
             g.alpha = alpha;
             g.rescale = 1.0 / mult;
+            if (log) {   /* rescaleGammaLogLk, NJ.tcc:5337-5357: the summary and the per-site table of the nCat x nPos likelihoods above */
+                log->line("Gamma(%d) LogLk = %.3f alpha = %.3f rescaling lengths by %.3f", (int) nCat, g.loglk, alpha, 1 / mult);
+                std::string text = StageLog::format("Gamma%dLogLk\t%.3f\tApproximate\tAlpha\t%.3f\tRescale\t%.3f\n", (int) nCat, g.loglk, alpha, 1 / mult);
+                text += StageLog::format("Gamma%d\tSite\tLogLk", (int) nCat);
+                for (int32_t i = 0; i < nCat; i++) text += StageLog::format("\tr=%.3f", (double) rates[(size_t) i] / mult);
+                text += "\n";
+                for (int64_t p = 0; p < nPos; p++) {
+                    text += StageLog::format("Gamma%d\t%lld\t%.3f", (int) nCat, (long long) p, gammaSites[(size_t) p]);
+                    for (int32_t i = 0; i < nCat; i++) text += StageLog::format("\t%.3f", siteLoglk[(size_t) (nPos * i + p)]);
+                    text += "\n";
+                }
+                log->text(text);
+            }
             std::vector<REAL> bl((size_t) nNodes);
             getLengths(bl.data());
             for (REAL &x: bl) x = (REAL) ((double) x * g.rescale);   /* branchlength[i] *= scale */
@@ -527,6 +544,7 @@ namespace veryfasttree {
             int64_t nSplits = 0, nBadSplits = 0;
             double worstDelta = 0;           /* dWorstDeltaUnconstrained */
             std::vector<double> support;     /* per node, -1 where there is none */
+            std::vector<char> bad;           /* per node, 1 = a bad split */
         };
 
         /* testSplitsML (NJ.tcc:6800-6999) without constraints: every internal split's three quartet likelihoods in one
@@ -551,6 +569,7 @@ namespace veryfasttree {
                                    loglk.data(), nBootstrap, col, nBootstrap > 0 ? sup.data() : nullptr, nullptr));
             SplitTests out;
             out.support.assign((size_t) nNodes, -1.0);
+            out.bad.assign((size_t) nNodes, 0);
             for (int64_t k = 0; k < n; k++) {
                 const double *l = &loglk[(size_t) (3 * k)];
                 int choice;
@@ -560,6 +579,7 @@ namespace veryfasttree {
                 const bool bad = l[choice] > l[0] + 0.1;   /* Constants::treeLogLkDelta */
                 out.nSplits++;
                 if (bad) {
+                    out.bad[(size_t) nodes[(size_t) k]] = 1;
                     out.nBadSplits++;
                     out.worstDelta = std::max(out.worstDelta, l[choice] - l[0]);
                 }
@@ -1174,6 +1194,41 @@ namespace veryfasttree {
         /* treePartitioning: roots of the subtrees, in the order the reference hands them to its threads */
         std::vector<int64_t> treePartitioning(int penalty, int threads, int window = 50) {
             return partitionTree(nNodes, child, root, order, penalty, threads, window, &partitionSpeedup);
+        }
+
+        /* The log's "Bad splits" at threads > 1.  testSplitsMinEvo and testSplitsML walk the subtrees of treePartitioning(0) first and then
+           add every subtree walk's nSplits - not its nBadSplits - to the bad splits (NJ.tcc:6785-6787, :6839-6841); the walk from the root
+           that follows counts the nodes outside the subtrees as usual.  mask[v] = 1: node v lies in one of those subtrees, its root
+           included, so the reference's summary counts it as bad whatever its quartet says.  child[nNodes][3] as in partitionTree. */
+        static std::vector<char> subtreeSplitMask(int64_t nSeqs, int64_t nNodes, const std::vector<int64_t> &child, int64_t root, int threads) {
+            std::vector<int64_t> order;
+            std::vector<std::pair<int64_t, int> > stack(1, std::make_pair(root, 0));
+            while (!stack.empty()) {   /* post-order of the internal nodes, children in stored order, the root last */
+                const int64_t v = stack.back().first;
+                const int k = stack.back().second;
+                if (k < 3 && child[(size_t) (3 * v + k)] >= 0) {
+                    stack.back().second++;
+                    stack.push_back(std::make_pair(child[(size_t) (3 * v + k)], 0));
+                } else {
+                    stack.pop_back();
+                    if (child[(size_t) (3 * v)] >= 0) order.push_back(v);
+                }
+            }
+            double speedup = 0;
+            std::vector<char> mask((size_t) nNodes, 0);
+            std::vector<int64_t> below;
+            for (int64_t r: partitionTree(nNodes, child, root, order, /*penalty*/0, threads, 50, &speedup)) {
+                if (r < nSeqs || r >= nNodes || r == root) continue;
+                below.assign(1, r);
+                while (!below.empty()) {
+                    const int64_t v = below.back();
+                    below.pop_back();
+                    mask[(size_t) v] = 1;
+                    for (int k = 0; k < 2; k++)
+                        if (child[(size_t) (3 * v + k)] >= nSeqs) below.push_back(child[(size_t) (3 * v + k)]);
+                }
+            }
+            return mask;
         }
 
         /* the algorithm itself, on plain arrays (exported as vft_tree_partitioning for the CPU test that pins it to the reference's

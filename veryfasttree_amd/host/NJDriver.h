@@ -41,6 +41,7 @@
 #include "PseudoDistances.h"
 #include "KnuthRng.h"
 #include "AAModels.h"
+#include "StageLog.h"
 
 namespace veryfasttree {
 
@@ -777,6 +778,14 @@ namespace veryfasttree {
                 const int64_t cnt = std::min<int64_t>(maxCall, nPairs - p0);
                 chkT("vft_profile_distances", [&]() { return vft_profile_distances(ctx, cnt, pi.data() + p0, pj.data() + p0, pd.data() + p0, pw.data() + p0); });
             }
+            meSplits = meBadSplits = 0;
+            meWorstDelta = 0;
+            std::vector<char> threadMask;   /* the reference's count of bad splits at more than one thread (MLLengths::subtreeSplitMask) */
+            if (log && opt.threads > 1) {
+                std::vector<int64_t> par, ch;
+                treeArrays(par, ch);
+                threadMask = MLLengths<REAL>::subtreeSplitMask(nSeqs, maxnode, ch, root, opt.threads);
+            }
             /* 3. branch lengths (double arithmetic, stored as numeric_t) */
             for (int64_t v = 0; v < maxnode; v++) {
                 if (v == root) continue;
@@ -789,6 +798,12 @@ namespace veryfasttree {
                     pseudoDistancesOfDevice<REAL>(6, pd.data() + f, pw.data() + f, opt.pseudoWeight, opt.scoredist, d);
                     /* qAB 0, qAC 1, qAD 2, qBC 3, qBD 4, qCD 5 */
                     branchlength[(size_t) v] = (REAL) ((d[1] + d[2] + d[3] + d[4]) / 4.0 - (d[0] + d[5]) / 2.0);
+                    if (log) {   /* testSplitsMinEvo (NJ.tcc:6660-6710, no constraints) reads the same six distances of the same quartet */
+                        const double delta = (d[0] + d[5]) - std::min(d[1] + d[4], d[2] + d[3]);
+                        meSplits++;
+                        if (delta > 1e-6) meWorstDelta = std::max(meWorstDelta, delta);
+                        if (delta > 1e-6 || (!threadMask.empty() && threadMask[(size_t) v])) meBadSplits++;
+                    }
                 }
             }
         }
@@ -855,7 +870,14 @@ namespace veryfasttree {
                     const int64_t nChange = opt.threads > 1 ? tree.doNNIThreaded(prm, stats, maxDelta, opt.threads) : tree.doNNI(prm, stats, maxDelta);
                     meNNIRoundsDone++;
                     total += nChange;
-                    if (nChange == 0) bConverged = true;
+                    if (log) {   /* VeryFastTreeImpl.tcc:171: the lengths are the NJ phase's, no minimum-evolution move assigns one */
+                        adoptTree(tree.parents(), tree.children());
+                        logTree("ME_NNI", i + 1);
+                    }
+                    if (nChange == 0) {
+                        bConverged = true;
+                        if (log) log->line("Min_evolution NNIs converged at round %lld -- skipping some rounds", (long long) (i + 1));   /* :179-183 */
+                    }
                 }
                 /* SPR rounds sit between thirds of the NNI rounds (VeryFastTreeImpl.tcc:187-198) */
                 if (sprRemaining > 0 && sprBehindNNIRound(i, nniToDo, spr)) {
@@ -865,6 +887,10 @@ namespace veryfasttree {
                         meSPRs += tree.doSPR(opt.scoredist, opt.sprLength);
                         meSPRSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
                         if (std::getenv("VFT_STAGE_TRACE")) fprintf(stderr, "[stage] SPR round done: %.1f s of SPR so far, %lld moves\n", meSPRSeconds, (long long) meSPRs);
+                    }
+                    if (log) {   /* VeryFastTreeImpl.tcc:192 */
+                        adoptTree(tree.parents(), tree.children());
+                        logTree("ME_SPR", spr - sprRemaining + 1);
                     }
                     sprRemaining--;
                     bConverged = false;
@@ -876,6 +902,10 @@ namespace veryfasttree {
                 const std::chrono::steady_clock::time_point ts = std::chrono::steady_clock::now();
                 meSPRs += tree.doSPR(opt.scoredist, opt.sprLength);
                 meSPRSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
+                if (log) {   /* VeryFastTreeImpl.tcc:202 */
+                    adoptTree(tree.parents(), tree.children());
+                    logTree("ME_SPR", spr - sprRemaining + 1);
+                }
                 sprRemaining--;
             }
             meSPRSteps = tree.sprSteps;
@@ -884,6 +914,7 @@ namespace veryfasttree {
             laneGathers += tree.laneGathers;
             laneGatherBytes += tree.laneGatherBytes;
             adoptTree(tree.parents(), tree.children());
+            meNNIs = total;
             return total;
         }
 
@@ -934,6 +965,8 @@ namespace veryfasttree {
                 ml.recomputeAverageProfiles();
             } else if (reaverage) ml.recomputeAverageProfiles();
             std::vector<double> loglk;
+            /* "LogLk ~=" where the posteriors are approximate (VeryFastTreeImpl.tcc:289, :331, :376: proteins without exactML) */
+            const char *approxMark = log && opt.aaModel && vft_get_approx_ml(ctx) ? "~" : "";
             const bool parallelLengths = opt.parallelLengths;
             const int64_t maxRound = mllen ? (int64_t) (0.5 + std::log((double) nSeqs) / std::log(2.0)) : 0;
             std::vector<REAL> old((size_t) maxnode);
@@ -948,13 +981,20 @@ namespace veryfasttree {
                 ml.getLengths(branchlength.data());
                 double dMaxChange = 0;
                 for (int64_t v = 0; v < maxnode; v++) dMaxChange = std::max(dMaxChange, std::fabs((double) old[(size_t) v] - (double) branchlength[(size_t) v]));
+                logTree("ML_Lengths");   /* VeryFastTreeImpl.tcc:273 (its format holds no number) */
                 loglk.push_back(ml.treeLogLk(nPos, nLeafGaps));
                 /* (the reference never updates its dLastLogLk, so the likelihood clause of its test cannot fire) */
                 const bool converged = iRound > 1 && dMaxChange < 0.001;
+                if (log) {   /* VeryFastTreeImpl.tcc:285-298 */
+                    log->line("%lld rounds ML lengths: LogLk %s= %.3f Max-change %.4f%s Time %.2f", (long long) iRound, approxMark, loglk.back(), dMaxChange,
+                              converged ? " (converged)" : "", log->clock());
+                    log->line("TreeLogLk\tLength%lld\t%.4f\tMaxChange\t%.4f", (long long) iRound, loglk.back(), dMaxChange);
+                }
                 if (iRound == 1) {
                     if (gtr) fitGtr(ml, nLeafGaps, ftol, atol);           /* `-gtr`: Jukes-Cantor up to here (VeryFastTreeImpl.tcc:299-302) */
                     ml.setMLRates(nRateCats, nPos, mlRates, mlRateCat);   /* VeryFastTreeImpl.tcc:299-305 */
                     ratesSet = nRateCats > 1;
+                    logMLRates(ml, nRateCats);
                 }
                 if (converged) break;
             }
@@ -966,6 +1006,10 @@ namespace veryfasttree {
                 const int64_t MLnniToDo = mlNNIRoundsToDo(nSeqs, opt.mlNNIRounds);
                 if (opt.threads > 1) ml.optimizeRoundThreaded(ftol, atol, opt.threads);
                 else ml.optimizeRound(ftol, atol);
+                if (log) {   /* VeryFastTreeImpl.tcc:315 */
+                    ml.getLengths(branchlength.data());
+                    logTree("ML_Lengths", 1);
+                }
                 typename MLLengths<REAL>::NNIParams prm;
                 prm.useML = true;
                 prm.ftol = ftol;
@@ -979,23 +1023,39 @@ namespace veryfasttree {
                 mlNNIs = 0;
                 for (int64_t iMLnni = 0; iMLnni < MLnniToDo; iMLnni++) {
                     double maxDelta;
+                    int64_t changes;
                     {
                         const std::chrono::steady_clock::time_point ts = std::chrono::steady_clock::now();
-                        mlNNIs += opt.threads > 1 ? ml.doNNIThreaded(prm, stats, maxDelta, opt.threads) : ml.doNNI(prm, stats, maxDelta);
+                        changes = opt.threads > 1 ? ml.doNNIThreaded(prm, stats, maxDelta, opt.threads) : ml.doNNI(prm, stats, maxDelta);
+                        mlNNIs += changes;
                         mlNNISeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
+                    }
+                    if (log) {   /* VeryFastTreeImpl.tcc:322 */
+                        ml.getLengths(branchlength.data());
+                        adoptTree(ml.parents(), ml.children());
+                        logTree("ML_NNI", iMLnni + 1);
                     }
                     const double ll = ml.treeLogLk(nPos, nLeafGaps);
                     loglk.push_back(ll);
                     const bool bConvergedHere = iMLnni > 0 && (ll < lastloglk + 0.1 || maxDelta < 0.1);
+                    if (log) {   /* VeryFastTreeImpl.tcc:327-338 */
+                        log->line("ML-NNI round %lld: LogLk %s= %.3f NNIs %lld max delta %.2f Time %.2f%s", (long long) (iMLnni + 1), approxMark, ll,
+                                  (long long) changes, maxDelta, log->clock(), bConverged ? " (final)" : "");
+                        log->line("TreeLogLk\tML_NNI%lld\t%.4f\tMaxChange\t%.4f", (long long) (iMLnni + 1), ll, maxDelta);
+                    }
                     if (bConverged) break;
                     if (bConvergedHere) bConverged = true;
-                    if (bConverged || iMLnni == MLnniToDo - 2) ml.initNNIStats(stats);
+                    if (bConverged || iMLnni == MLnniToDo - 2) {
+                        ml.initNNIStats(stats);
+                        if (log) log->line("Turning off heuristics for final round of ML NNIs%s", bConvergedHere ? " (converged)" : "");   /* :349-352 */
+                    }
                     lastloglk = ll;
                     if (iMLnni == 0 && !ratesSet) {
                         const std::chrono::steady_clock::time_point ts = std::chrono::steady_clock::now();
                         if (gtr && !gtrFitted) fitGtr(ml, nLeafGaps, ftol, atol);
                         ml.setMLRates(nRateCats, nPos, mlRates, mlRateCat);
                         ratesSet = nRateCats > 1;
+                        logMLRates(ml, nRateCats);   /* VeryFastTreeImpl.tcc:360-361 */
                         mlModelSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
                     }
                 }
@@ -1004,13 +1064,20 @@ namespace veryfasttree {
                 loglk.push_back(ml.treeLogLk(nPos, nLeafGaps));   /* "TreeLogLk ML_Lengths2" */
                 ml.getLengths(branchlength.data());
                 adoptTree(ml.parents(), ml.children());
+                if (log) {   /* VeryFastTreeImpl.tcc:371-382 */
+                    logTree("ML_Lengths", 2);
+                    log->line("Optimize all lengths: LogLk %s= %.3f Time %.2f", approxMark, loglk.back(), log->clock());
+                    log->line("TreeLogLk\tML_Lengths%d\t%.4f", 2, loglk.back());
+                }
             }
-            if (nBootstrap > 0 && nSeqs > 3) {
+            /* (the reference also tests the splits of a run without supports that made ML NNIs, for its summary's "Bad splits" alone,
+               VeryFastTreeImpl.tcc:387: here only when that summary is written) */
+            if ((nBootstrap > 0 || (log && mlNNI && !opt.fastest)) && nSeqs > 3) {
                 /* testSplitsML (VeryFastTreeImpl.tcc:396-398): SH-like supports from the same column resamples the
                    minimum-evolution supports would use (resampleColumns, NJ.tcc:705-727: Knuth's generator from its
                    default state) */
                 KnuthRng rng;
-                std::vector<int32_t> col((size_t) nBootstrap * nPos);
+                std::vector<int32_t> col((size_t) (nBootstrap > 0 ? nBootstrap : 0) * nPos);
                 for (size_t t = 0; t < col.size(); t++) {
                     int64_t pos = (int64_t) (rng.rand() * nPos);
                     if (pos < 0) pos = 0;
@@ -1020,14 +1087,20 @@ namespace veryfasttree {
                 const std::chrono::steady_clock::time_point ts = std::chrono::steady_clock::now();
                 const typename MLLengths<REAL>::SplitTests st = ml.testSplits(ftol, atol, nBootstrap, col.data(), /*alwaysSecondPass*/opt.mlAccuracy > 1);   /* NJ.tcc:6934, :6940 */
                 mlSupportSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
-                support = st.support;
+                if (nBootstrap > 0) support = st.support;
                 mlBadSplits = st.nBadSplits;
+                if (log && opt.threads > 1) {   /* the reference's count at more than one thread (MLLengths::subtreeSplitMask) */
+                    const std::vector<char> mask = MLLengths<REAL>::subtreeSplitMask(nSeqs, maxnode, ml.children(), root, opt.threads);
+                    mlBadSplits = 0;
+                    for (int64_t v = nSeqs; v < maxnode; v++)
+                        if (v != root && (mask[(size_t) v] || st.bad[(size_t) v])) mlBadSplits++;
+                }
                 mlSplits = st.nSplits;
                 mlWorstDelta = st.worstDelta;
             }
             if (opt.gamma && nRateCats > 1) {   /* `-gamma` (VeryFastTreeImpl.tcc:391-394): after the supports */
                 /* (Jukes-Cantor only: treeLogLk's per-site gap terms, NJ.tcc:5236-5252) */
-                const typename MLLengths<REAL>::GammaFit g = ml.branchlengthScale(nRateCats, nPos, mlRates, mlRateCat, nLeafGaps >= 0 ? gapsPerPos.data() : nullptr);
+                const typename MLLengths<REAL>::GammaFit g = ml.branchlengthScale(nRateCats, nPos, mlRates, mlRateCat, nLeafGaps >= 0 ? gapsPerPos.data() : nullptr, log);
                 gammaFit[0] = g.loglk;
                 gammaFit[1] = g.alpha;
                 gammaFit[2] = g.rescale;
@@ -1047,6 +1120,25 @@ namespace veryfasttree {
             for (int i = 0; i < 4; i++) gtrFreq[i] = g.freq[i];
             gtrFitted = true;
             nLeafGaps = -1;   /* treeLogLk's Jukes-Cantor correction is gone with the transition matrix */
+            if (log) {   /* setMLGtr, NJ.tcc:6490-6496 */
+                log->line("GTR Frequencies: %.4f %.4f %.4f %.4f", gtrFreq[0], gtrFreq[1], gtrFreq[2], gtrFreq[3]);
+                log->line("GTR rates(ac ag at cg ct gt) %.4f %.4f %.4f %.4f %.4f %.4f", gtrRates[0], gtrRates[1], gtrRates[2], gtrRates[3], gtrRates[4], gtrRates[5]);
+            }
+        }
+
+        /* what setMLRates (NJ.tcc:5480-5483) and logMLRates (NJ.tcc:5497-5514) print once the categories are fitted */
+        void logMLRates(const MLLengths<REAL> &ml, int32_t nRateCats) {
+            if (!log) return;
+            if (nRateCats > 1) {
+                log->line("Switched to using %d rate categories (CAT approximation)", (int) nRateCats);
+                log->line("Rate categories were divided by %.3f so that average rate = 1.0", ml.avgRate);
+                log->line("CAT-based log-likelihoods may not be comparable across runs");
+            }
+            std::string text = StageLog::format("NCategories%lld\nRates", (long long) mlRates.size());
+            for (const REAL r: mlRates) text += StageLog::format(" %f", (double) r);
+            text += "\nSiteCategories";
+            for (const int64_t c: mlRateCat) text += StageLog::format(" %lld", (long long) (c + 1));
+            log->text(text + "\n");
         }
 
         int64_t mlNNIs = 0;
@@ -1066,7 +1158,7 @@ namespace veryfasttree {
            names[k] = name of alignment row k; uniqueFirst[u] = row of unique sequence u; alnNext[k] = next row with the
            same sequence or -1 (Alignment.cpp:494-526). */
         std::string newick(const std::vector<std::string> &names, const std::vector<int64_t> &uniqueFirst,
-                           const std::vector<int64_t> &alnNext) const {
+                           const std::vector<int64_t> &alnNext, bool showSupport = true) const {
             if (root < 0) throw std::invalid_argument("NJDriver::newick before finishRoot");
             const char *fmt = sizeof(REAL) == 4 ? "%.5f" : "%.9f";
             std::string out;
@@ -1093,7 +1185,7 @@ namespace veryfasttree {
                 } else if (end) {
                     if (node == root) out += ")";
                     else {
-                        if (!support.empty()) {   /* bShowSupport, NJ.tcc:2776-2777 */
+                        if (showSupport && !support.empty()) {   /* bShowSupport, NJ.tcc:2776-2777 */
                             snprintf(buf, sizeof buf, ")%.3f:", support[(size_t) node]);
                             out += buf;
                         } else out += "):";
@@ -1116,7 +1208,36 @@ namespace veryfasttree {
             return out;
         }
 
+        /* ---- `-log` (host/StageLog.h): null = no log - nothing below formats a tree or counts a split.  The names and the duplicate
+           lists are what newick() takes; they stay the caller's. */
+        StageLog *log = nullptr;
+        void setLog(StageLog *sink, const std::vector<std::string> *names, const std::vector<int64_t> *uniqueFirst, const std::vector<int64_t> *alnNext) {
+            log = sink;
+            logNames = names;
+            logUniqueFirst = uniqueFirst;
+            logAlnNext = alnNext;
+        }
+
+        /* logTree (NJ.tcc:5516-5522): `<tag>[<number>]\t` and printNJ without supports - branchlength[] as it stands */
+        void logTree(const char *tag, int64_t number = -1) {
+            if (!log) return;
+            log->text(std::string(tag) + (number >= 0 ? std::to_string(number) : std::string()) + "\t" + newick(*logNames, *logUniqueFirst, *logAlnNext, false) + "\n");
+        }
+
+        /* totalLen (NJ.tcc:290-296) */
+        double totalLen() const {
+            double total = 0;
+            for (int64_t v = 0; v < maxnode; v++) total += std::fabs((double) branchlength[(size_t) v]);
+            return total;
+        }
+
+        int64_t meNNIs = 0;                         /* "NNI: %d" of the log's summary (VeryFastTreeImpl.tcc:447) */
+        int64_t meSplits = 0, meBadSplits = 0;      /* testSplitsMinEvo (NJ.tcc:6639-6750): counted by updateBranchLengths when a log is written */
+        double meWorstDelta = 0;
+
     private:
+        const std::vector<std::string> *logNames = nullptr;
+        const std::vector<int64_t> *logUniqueFirst = nullptr, *logAlnNext = nullptr;
         int64_t root = -1, rootChild[3] = {-1, -1, -1};
         bool upReady = false;
         std::vector<double> support;   /* per node, filled by computeSupports */

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <chrono>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -17,6 +18,7 @@
 #include "AAModels.h"
 #include "SeqMatrix.h"
 #include "ReadTree.h"
+#include "StageLog.h"
 
 // CRC-32 (the zlib polynomial) of the last join order this process produced, per chunk of joins: lets a caller that only asked
 // for the tree (vft_nj_newick at a million sequences) compare the join order with a prefix of the reference's `Join` lines
@@ -170,6 +172,33 @@ extern "C" int vft_nj_last_stage_seconds(double *seconds, int64_t *counts) {
     if (counts)
         for (int i = 0; i < 4; i++) counts[i] = gLanes[i];
     return VFT_OK;
+}
+
+/* `-log` (vft_nj_set_log): the descriptor the next runs write the reference's log lines to; -1 = none.  Process state, like the
+   other last-run records above. */
+static int gLogFd = -1;
+
+extern "C" int vft_nj_set_log(int32_t fd) {
+    gLogFd = fd < 0 ? -1 : fd;
+    return VFT_OK;
+}
+
+extern "C" int vft_nj_get_log() { return gLogFd; }
+
+/* the log's first line: what it holds of the reference's log and what it leaves out (every comparison skips it) */
+static const char kLogHeader[] =
+        "# veryfasttree-amd log: the reference's stage trees, TreeLogLk, GTR, rate-category and Gamma lines, its clock lines and summary; "
+        "not written: Command, version and option echo, Dist/N**2, Top hits, Max-lk operations, progress and warning texts, "
+        "anything above the default verbosity\n";
+
+/* the sink of a run, or none: logging is off, or this is not rank 0 of a communicator */
+static std::unique_ptr<veryfasttree::StageLog> openLog(const vft_comm *comm) {
+    std::unique_ptr<veryfasttree::StageLog> sink;
+    if (gLogFd >= 0 && !(comm && comm->world > 1 && comm->rank > 0)) {
+        sink.reset(new veryfasttree::StageLog(gLogFd));
+        sink->text(kLogHeader);
+    }
+    return sink;
 }
 
 static veryfasttree::NJOptions toOptions(const vft_nj_options *o) {
@@ -349,7 +378,17 @@ static std::string runTree(vft_ctx *ctx, const uint8_t *codes, int64_t nSeqs, in
     /* `-intree`: the text is parsed before anything reaches the device - a malformed tree costs no upload */
     veryfasttree::ReadTreeResult tree;
     if (o && o->intree) tree = readTreeText(o->intree, nAll, names, uniqueFirst, alnNext, nSeqs);
+    /* the log opens behind every refusal - the option checks of the caller, the parse above: a run that is refused writes nothing */
+    const std::unique_ptr<veryfasttree::StageLog> sink = openLog(o ? o->comm : nullptr);
+    veryfasttree::StageLog *const log = sink.get();
     veryfasttree::NJDriver<REAL> drv(ctx, codes, nSeqs, nPos, toOptions(o));
+    const std::vector<std::string> nm = splitNames(names, nAll);
+    const std::vector<int64_t> uf(uniqueFirst, uniqueFirst + nSeqs), an(alnNext, alnNext + nAll);
+    drv.setLog(log, &nm, &uf, &an);
+    /* the rounds the reference announces (VeryFastTreeImpl.tcc:145-149) */
+    const int64_t nniToDo = o && o->me_nni ? veryfasttree::meNNIRoundsToDo(nSeqs, o->nni_rounds > 0 ? o->nni_rounds : 0) : 0;
+    const int64_t sprToDo = o && o->me_nni ? o->spr : 0;
+    const int64_t mlNNIToDo = o && o->ml_nni ? veryfasttree::mlNNIRoundsToDo(nSeqs, o->ml_nni_rounds > 0 ? o->ml_nni_rounds : 0) : 0;
     for (double &x: gStage) x = 0;
     auto now = []() { return std::chrono::steady_clock::now(); };
     auto since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double>(now() - t).count(); };
@@ -363,6 +402,12 @@ static std::string runTree(vft_ctx *ctx, const uint8_t *codes, int64_t nSeqs, in
         drv.finishRoot();
     }
     gStage[0] = since(t0);
+    if (log) {
+        drv.logTree("NJ");   /* VeryFastTreeImpl.tcc:143 */
+        if (!(o && o->intree)) log->line("Initial topology in %.2f seconds", log->clock());   /* :150-153 */
+        if (sprToDo > 0 || nniToDo > 0 || mlNNIToDo > 0)   /* :154-158 */
+            log->line("Refining topology: %lld rounds ME-NNIs, %d rounds ME-SPRs, %lld rounds ML-NNIs", (long long) nniToDo, (int) sprToDo, (long long) mlNNIToDo);
+    }
     static const bool stageTrace = std::getenv("VFT_STAGE_TRACE") != nullptr;   /* tools: the stages as they end, on stderr */
     if (stageTrace) fprintf(stderr, "[stage] NJ phase done after %.1f s\n", gStage[0]);
     t0 = now();
@@ -372,6 +417,10 @@ static std::string runTree(vft_ctx *ctx, const uint8_t *codes, int64_t nSeqs, in
     gStage[2] = drv.meSPRSeconds;
     t0 = now();
     if (meLengths) drv.updateBranchLengths();
+    if (log && meLengths) {
+        drv.logTree("ME_Lengths");   /* VeryFastTreeImpl.tcc:213 */
+        log->line("Total branch-length %.3f after %.2f sec", drv.totalLen(), log->clock());   /* :215-220 */
+    }
     const bool ml = o && (o->mllen || o->ml_nni);
     if (nBootstrap > 0 && !ml) drv.computeSupports(nBootstrap);
     gStage[3] = since(t0);
@@ -402,8 +451,20 @@ static std::string runTree(vft_ctx *ctx, const uint8_t *codes, int64_t nSeqs, in
     gLaneExchange[0] = drv.laneGathers;
     gLaneExchange[1] = drv.laneGatherBytes;
     drv.report();
-    const std::vector<std::string> nm = splitNames(names, nAll);
-    return drv.newick(nm, std::vector<int64_t>(uniqueFirst, uniqueFirst + nSeqs), std::vector<int64_t>(alnNext, alnNext + nAll));
+    if (log) {   /* the summary (VeryFastTreeImpl.tcc:403-414, :425-450) */
+        const int64_t bad = ml ? drv.mlBadSplits : drv.meBadSplits;
+        const int64_t splits = ml ? drv.mlSplits : drv.meSplits;
+        const double worst = ml ? drv.mlWorstDelta : drv.meWorstDelta;
+        std::string total = veryfasttree::StageLog::format("Total time: %.2f seconds Unique: %lld/%lld Bad splits: %lld/%lld", log->clock(), (long long) nSeqs,
+                                                           (long long) nAll, (long long) bad, (long long) splits);
+        if (worst > 0) total += veryfasttree::StageLog::format(" Worst delta-%s %.3f", ml ? "LogLk" : "Len", worst);
+        log->text(total + "\n");
+        if (!(o && o->threads > 1) && (nniToDo > 0 || sprToDo > 0 || mlNNIToDo > 0))   /* :446-450: nothing of this block at more than one thread */
+            log->line("NNI: %lld SPR: %lld ML-NNI: %lld", (long long) drv.meNNIs, (long long) drv.meSPRs, (long long) drv.mlNNIs);
+    }
+    const std::string text = drv.newick(nm, uf, an);
+    if (log) log->line("TreeCompleted");   /* :469 */
+    return text;
 }
 
 extern "C" int vft_nj_ml_newick(vft_ctx *ctx, const uint8_t *codes, int64_t nSeqs, int64_t nPos, int32_t precision,
@@ -654,6 +715,7 @@ extern "C" int vft_nj_make_matrix(vft_ctx *ctx, int64_t nSeqs, int32_t precision
         if (!ctx || !names || nSeqs < 1 || fd < 0 || (precision != 4 && precision != 8)) throw std::runtime_error("vft_nj_make_matrix: bad arguments");
         if (comm && comm->world > 1)
             throw std::runtime_error("-makematrix runs on one GPU: the matrix is not split over the ranks of a communicator (and is not approximated)");
+        openLog(comm);   /* `-makematrix` writes the log's first line and nothing else */
         std::vector<std::string> nm;
         const char *p = names;
         for (int64_t k = 0; k < nSeqs; k++) {

@@ -12,7 +12,8 @@ import numpy as np
 RefRun = collections.namedtuple("RefRun", "n_codes dtype n_bootstrap kwargs other")
 RefRun.__doc__ = """n_codes: 4 with -nt, else 20; dtype: np.float64 with -double-precision, else np.float32 (also kwargs["dtype"]);
 n_bootstrap: `-boot N`, 0 with -nosupport, else 1000; kwargs: the keyword arguments of nj_newick, only those the flags ask for;
-other: what nj_newick has no keyword for and the caller has to act on - makematrix, rawdist, notop (True), seed (int)."""
+other: what nj_newick has no keyword for and the caller has to act on - makematrix, rawdist, notop (True), seed (int), log (the file
+name of `-log FILE`: this module opens no file - the caller hands it to nj_newick(log=...))."""
 
 SWITCHES = ("-nt", "-double-precision", "-lg", "-wag", "-gtr", "-gamma", "-noml", "-nome", "-mllen", "-nocat", "-nosupport", "-slow",
             "-fastest", "-2nd", "-no2nd", "-notop", "-slownni", "-makematrix", "-rawdist", "-approxml", "-mlapprox")
@@ -31,6 +32,21 @@ def zero_round_stages(me_nni, spr, ml_nni, nni_rounds, ml_nni_rounds):
     if ml_nni_rounds is not None and int(ml_nni_rounds) == 0:
         ml_nni = 0
     return me_nni, spr, ml_nni
+
+
+def file_of(flags, flag):
+    """(the flags without `flag FILE`, FILE or None) for a flag that takes a file name (-log, -intree); a ValueError that names the flag
+    where the name is missing or the flag is given twice.  Callers that keep flags of their own next to the reference's (tools/nj_tree.py)
+    take the file out with this before they look at the rest."""
+    flags = list(flags)
+    if flags.count(flag) > 1:
+        raise ValueError("%s is given twice" % flag)
+    if flag not in flags:
+        return flags, None
+    k = flags.index(flag)
+    if k + 1 >= len(flags):
+        raise ValueError("%s needs a file" % flag)
+    return flags[:k] + flags[k + 2:], flags[k + 1]
 
 
 def _parse(flags):
@@ -64,11 +80,6 @@ def _parse(flags):
             if not (weight >= 0.0) or math.isinf(weight):
                 raise ValueError("-pseudo takes a weight >= 0, not '%s'" % flags[k - 1])
             seen[flag] = weight
-        elif flag == "-intree":
-            if k >= len(flags):
-                raise ValueError("-intree needs a file")
-            seen[flag] = flags[k]
-            k += 1
         else:
             raise ValueError("%s: not a flag of the reference that this backend knows" % flag)
     return seen
@@ -79,7 +90,12 @@ def from_reference_flags(flags, threads=None, intree_text=None):
     it (the fixtures store it apart).  intree_text: the Newick text of `-intree FILE` - this function opens no file, so flags that name
     one need the text; the text alone is taken as `-intree`.  An unknown flag, a flag without its number and a number out of range are
     a ValueError that names the flag."""
-    f = _parse(flags.split() if isinstance(flags, str) else list(flags))
+    flags, files = flags.split() if isinstance(flags, str) else list(flags), {}
+    for flag in ("-intree", "-log"):
+        flags, name = file_of(flags, flag)
+        if name is not None:
+            files[flag] = name
+    f = dict(_parse(flags), **files)
     nt = "-nt" in f
     dtype = np.float64 if "-double-precision" in f else np.float32
     kw = dict(dtype=dtype)
@@ -134,5 +150,5 @@ def from_reference_flags(flags, threads=None, intree_text=None):
         kw["approx_ml"] = True
     kw.update({key: f[flag] for flag, key in THOROUGH.items() if f.get(flag)})   # (a count of 0 has become the switches above)
     n_bootstrap = 0 if "-nosupport" in f else f.get("-boot", 1000)
-    other = {key: f["-" + key] for key in ("makematrix", "rawdist", "notop", "seed") if "-" + key in f}
+    other = {key: f["-" + key] for key in ("makematrix", "rawdist", "notop", "seed", "log") if "-" + key in f}
     return RefRun(4 if nt else 20, dtype, n_bootstrap, kw, other)
