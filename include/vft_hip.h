@@ -110,6 +110,16 @@ int vft_set_near_posteriors(vft_ctx *ctx, const void *near_p, const void *near_f
    and ignores it, as the reference does under -nt.  vft_get_approx_ml returns the switch (0 / 1). */
 int vft_set_approx_ml(vft_ctx *ctx, int32_t on);
 int vft_get_approx_ml(vft_ctx *ctx);
+/* `-rawdist` (the reference's Options::logdist = false): the minimum-evolution stages compare UNCORRECTED profile distances.  A switch
+   on the context like vft_set_approx_ml, off by default; vft_get_raw_distances returns it (0 / 1).  It is read in the two places where
+   this library log-corrects a distance itself: vft_split_supports (the resamples of the local bootstrap are compared without
+   logCorrect, NJ.tcc:660, :692 - on the device and in the host's decision of near-ties) and the walk server, whose commands then
+   carry bit 23 (csrc/vft_kernels_walk.h, VFT_WS_RAW_BIT): the workgroups compare a dual command's six distances as they are.  With
+   the switch off every call is answered bit for bit as before.  vft_walk_scoredist and the `scoredist` of vft_walk_submit_dual keep
+   their meaning (0 Jukes-Cantor, 1 scoredist-like); the switch overrides both while it is on.  The host driver (include/vft_host.h)
+   reads the same switch for its own corrections.  vft_seq_matrix_rows has its own argument and does not read it. */
+int vft_set_raw_distances(vft_ctx *ctx, int32_t on);
+int vft_get_raw_distances(vft_ctx *ctx);
 /* Rate categories (NJ.h Rates: rates[n_rates], ratecat[n_pos]). */
 int vft_set_rates(vft_ctx *ctx, const void *rates, int32_t n_rates, const int64_t *ratecat);
 /* ML tolerances that the reference reads from Options inside the hot loops (Constants.h:26-39). */
@@ -560,7 +570,8 @@ int vft_ml_eval_count(vft_ctx *ctx, int64_t *evals);
    fraction of resamples in which the split beats both alternative pairings of the four profiles.  Any alignment the NJ
    phase takes (up to 10 240 columns): up to 1 706 columns one kernel holds the six pairs of a quartet in LDS, beyond
    that another takes them in passes of 3, 2 or 1 pairs (the same sums, the same supports); longer alignments are
-   refused with VFT_ERR_INVALID before any launch. */
+   refused with VFT_ERR_INVALID before any launch.  The distances of a resample are log-corrected (Jukes-Cantor without,
+   scoredist-like with a distance matrix) unless vft_set_raw_distances is on. */
 int vft_split_supports(vft_ctx *ctx, int64_t n, const int64_t *a, const int64_t *b, const int64_t *c, const int64_t *d,
                        int32_t n_boot, const int32_t *col, double *support);
 

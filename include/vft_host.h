@@ -65,7 +65,9 @@ typedef struct {
                                    after the first ML round, setMLGtr NJ.tcc:6436-6500; Jukes-Cantor until then) */
     int32_t aa_model;           /* amino-acid contexts (n_codes = 20): 0 = the caller installs its own matrices
                                    (vft_set_distance_matrix / vft_set_transition_matrix); 1 = JTT92 (the reference's
-                                   default), 2 = WAG01 (`-wag`), 3 = LG08 (`-lg`) (VeryFastTreeImpl.tcc:96-108).  With a
+                                   default), 2 = WAG01 (`-wag`), 3 = LG08 (`-lg`) (VeryFastTreeImpl.tcc:96-108); 4 = `-trans`:
+                                   the matrix set with vft_nj_set_aa_transition - without one the run is refused before
+                                   anything reaches the device, and on a nucleotide context it is refused too.  With a
                                    model the driver installs the BLOSUM45-derived distance matrix for the NJ /
                                    minimum-evolution phase (the reference's default for proteins, DistanceMatrix.tcc:33)
                                    with scoredist log-correction, and before the ML stage re-averages every profile in
@@ -265,6 +267,15 @@ int vft_nj_round_plan(int64_t n_seqs, int32_t nni_rounds, int32_t ml_nni_rounds,
    alpha, the factor every branch length was multiplied by (the reference's "Gamma(20) LogLk = .. alpha = .. rescaling lengths by ..") */
 int vft_nj_last_gamma(double *out);
 
+/* `-rawdist` (Options::logdist = false) for a tree: no member of vft_nj_options but a switch on the context, vft_set_raw_distances
+   (include/vft_hip.h), set before the run like vft_set_approx_ml.  The driver reads it once, when it starts, and decides in one place
+   (host/PseudoDistances.h, distCorrectionOf) between Jukes-Cantor, scoredist-like and no correction for every distance of the
+   minimum-evolution stages: the NNI criteria, the SPR chains and updateBranchLengths (correctedPairDistances, NJ.tcc:1484) - hence
+   the lengths the ML stage starts from; the local-bootstrap supports and the walk server's dual commands read the same switch
+   inside the HIP library.  `-pseudo` composes with it: the pseudocount step stays, the final correction goes.  Dual commands stay on.
+   The NJ phase and the ML stages never log-correct and do not change.  (The reference's two-sequence case of updateBranchLengths,
+   NJ.tcc:6566, has no counterpart: this driver refuses fewer than 3 sequences.)  vft_pseudo_distances keeps its `scoredist` (0 / 1). */
+
 /* `-log FILE`: the descriptor to which the following vft_nj_newick / vft_nj_ml_newick of this process write the reference's log lines
    (host/StageLog.h), each with write(2) as its stage finishes - a run that fails leaves the lines of the stages it
    completed.  fd < 0 switches logging off, which is the default; the descriptor stays the caller's (it is never closed here).  The
@@ -333,6 +344,31 @@ int vft_aa_model_tables(int32_t model, int32_t precision, double *stat, double *
 /* nearP[20][20] / nearFreq[20][20] of a built-in model (TransitionMatrix.tcc:227-279), what the driver hands to
    vft_set_near_posteriors beside the model for `-approxml`: numeric_t values held in double.  No device. */
 int vft_aa_near_tables(int32_t model, int32_t precision, double *near_p, double *near_freq);
+
+/* ---- `-trans FILE`: a caller's own amino-acid rate matrix (readAATransitionMatrix, TransitionMatrix.tcc:63-156)
+   vft_read_aa_transition: the parse alone (host/ReadTransition.h), pure host code - no device, and no file: `text` is the file's
+   text.  A header line `A<tab>R<tab>...<tab>V<tab>*`, then per amino acid its letter, its 20 rates and its stationary frequency.
+   It accepts what the reference accepts and refuses with the reference's checks and texts (tolerance 1e-5): the header, a row's
+   first field, too few fields, a frequency below the tolerance or a sum that is not 1, a diagonal that is not negative, a diagonal -
+   frequency dot product that is not -1, a negative off-diagonal entry, a column that does not sum to 0; a field that holds no number
+   is an error that names the amino acid.  matrix[400] is row-major as written, stat[20] the last column.  VFT_ERR_INVALID with
+   the message in err. */
+int vft_read_aa_transition(const char *text, double *matrix, double *stat, char *err, int32_t err_len);
+/* The matrix vft_nj_options.aa_model = 4 stands for.  PROCESS state, like vft_nj_set_log: it is copied here, read by every
+   tree run with aa_model = 4 that follows (installAAModel: the re-averaging basis, the transition matrix, `-approxml`'s near tables,
+   `-gamma`, `-log` as for a built-in model; the NJ / minimum-evolution stages use BLOSUM45 as for every protein run) and cleared
+   only by vft_nj_set_aa_transition(NULL, NULL) - no run clears it.  Frequencies must be positive and every entry finite
+   (VFT_ERR_INVALID, nothing is set); the reference's other checks are vft_read_aa_transition's.  A `-wag` / `-lg` next to
+   `-trans` is ignored by the reference: a caller passes 4.  vft_nj_get_aa_transition: 1 while a matrix is set. */
+int vft_nj_set_aa_transition(const double *matrix, const double *stat);
+int vft_nj_get_aa_transition(void);
+/* A built-in model's constants as they go into createTransitionMatrix: matrix[400] (diagonal included), stat[20]. */
+int vft_aa_model_matrix(int32_t model, double *matrix, double *stat);
+/* vft_aa_model_tables / vft_aa_near_tables for any matrix (createTransitionTables and nearPosteriorTables of host/AAModels.h as
+   they stand): the same outputs.  A built-in model's constants give that model's tables bit for bit. */
+int vft_aa_tables_from_matrix(const double *matrix, const double *stat_in, int32_t precision, double *stat, double *statinv, double *eigenval,
+                              double *codefreq, double *eigeninv, double *eigeninvT);
+int vft_aa_near_tables_from_matrix(const double *matrix, const double *stat_in, int32_t precision, double *near_p, double *near_freq);
 /* The default protein distance matrix (matrixBLOSUM45 + setupDistanceMatrix, DistanceMatrix.tcc:33-36, 102-155):
    distances[20][20], codefreq[20][20], eigenval[20], eigentot[20] as vft_set_distance_matrix takes them. */
 int vft_blosum45_tables(int32_t precision, double *distances, double *codefreq, double *eigenval, double *eigentot);

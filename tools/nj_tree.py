@@ -12,6 +12,8 @@ or - with -mllen - the tree of `VeryFastTree -nt -nome -mllen [-nocat | -cat N] 
     python tools/nj_tree.py in.fasta -full -spr 4 -mlacc 2 -slownni [-nni N] [-mlnni N] [-sprlength N] > tree.nwk   # the thorough search
     python tools/nj_tree.py in.fasta -aa [-wag | -lg] -full|-mllen -approxml > tree.nwk   # `VeryFastTree ... -approxml` (alias -mlapprox)
     python tools/nj_tree.py -makematrix [-rawdist] [-aa] [-double] in.fasta > matrix.txt   # `VeryFastTree [-nt] [-rawdist] [-double-precision] -makematrix`
+    python tools/nj_tree.py in.fasta [any mode above] -rawdist > tree.nwk   # `VeryFastTree ... -rawdist`: no log correction in the ME stages
+    python tools/nj_tree.py in.fasta -aa -full|-mllen -trans model.txt > tree.nwk   # `VeryFastTree -trans model.txt ...`: the ML stage under the file's rate matrix
     python tools/nj_tree.py in.fasta [any mode above] -log FILE > tree.nwk   # `VeryFastTree ... -log FILE`: stage trees, likelihoods, rates
 
 Neighbour joining with top hits on the device (veryfasttree_amd/host/NJDriver.h), the root, minimum-evolution branch
@@ -42,6 +44,12 @@ they end the program with a message.
 -approxml (or -mlapprox): the reference's option of that name - the posteriors of a protein run's ML stages skip the rotation where one
 state dominates and the rest follows the model's near-constant table (NJ.tcc:2390-2421).  Accepted and without effect for nucleotides
 and where no ML stage runs, as in the reference.
+-rawdist (for a tree): the reference's option of that name - the minimum-evolution NNIs, the SPR chains, the ME branch lengths and the
+local-bootstrap supports compare uncorrected profile distances (no Jukes-Cantor / scoredist-like logarithm).  Not read by the NJ phase
+and the ML stage, whose starting lengths it changes.
+-trans FILE: the reference's option of that name - an amino-acid rate matrix (header `A<tab>R<tab>...<tab>V<tab>*`, then per amino acid its
+letter, 20 rates, its stationary frequency) replaces JTT in the ML stage; a -wag / -lg beside it is ignored, as in the reference.  The
+file is checked as the reference checks it; proteins only.
 -log FILE: the reference's `-log FILE` - the tree after every stage (NJ, ME_NNI<k>, ME_SPR<k>, ME_Lengths, ML_Lengths<k>, ML_NNI<k>), the TreeLogLk
 lines, the GTR and rate-category lines, with -gamma the per-site Gamma20 table, the clock lines and the summary; the first line says what the
 reference logs and this backend does not (README "-log").  Each line is written when its stage ends.  With -makematrix: that first line alone.
@@ -112,7 +120,7 @@ def translate(args):
             sys.exit("-intree with -slow is not built")
         with open(start) as fh:
             intree = fh.read()
-    protein = any(a in args for a in ("-aa", "-jtt", "-wag", "-lg"))
+    protein = any(a in args for a in ("-aa", "-jtt", "-wag", "-lg", "-trans"))
     ref = [] if protein else ["-nt"]
     ref += ["-nome", "-mllen"] if mllen else [] if full else ["-noml", "-nome"]
     ref += ["-double-precision" if a == "-double" else a for a in args if a not in ("-full", "-mllen", "-aa", "-jtt", "-nj-lengths")]
@@ -125,9 +133,17 @@ def translate(args):
     for flag in NEEDS_FULL:
         if flag in args and not (full or (flag == "-mlacc" and mllen)):
             sys.exit("%s needs -full%s: without it the stage the option belongs to does not run" % (flag, " or -mllen" if flag == "-mlacc" else ""))
-    unbuilt = [key for key in run.other if key != "log"]
+    unbuilt = [key for key in run.other if key not in ("log", "rawdist", "trans")]
     if unbuilt:
         sys.exit("not built in this tool: -%s" % ", -".join(unbuilt))
+    if "trans" in run.other:   # (refflags opens no file: the text goes on as nj_newick's aa_trans)
+        try:
+            with open(run.other["trans"], "rb") as fh:
+                run.kwargs["aa_trans"] = fh.read()
+        except OSError as e:
+            sys.exit("-trans %s: %s" % (run.other["trans"], e.strerror))
+    if "rawdist" in run.other:
+        run.kwargs["rawdist"] = True
     nj_len = "-nj-lengths" in args
     return path, run._replace(n_bootstrap=0 if nj_len else run.n_bootstrap), nj_len
 
@@ -188,7 +204,7 @@ def main():
             raise
         sys.exit("-log %s: %s" % (e.filename, e.strerror))
     except VftError as e:
-        if "intree" not in run.kwargs and "-log" not in str(e):
+        if "intree" not in run.kwargs and "aa_trans" not in run.kwargs and "-log" not in str(e):
             raise
         sys.exit(str(e))
     label = "Round" if "ml_nni" in run.kwargs else "Length"   # of the TreeLogLk lines: by the stages that run, whatever -mlacc adds to a -mllen run

@@ -31,7 +31,7 @@ I32 = C.c_int32
 
 EXPORTS = [
     "vft_device_malloc", "vft_device_free", "vft_device_upload", "vft_create", "vft_destroy", "vft_allocation_count", "vft_last_error", "vft_set_stream", "vft_synchronize", "vft_upload_leaves",
-    "vft_set_distance_matrix", "vft_set_transition_matrix", "vft_set_rates", "vft_set_ml_limits", "vft_set_jc_exact", "vft_set_near_posteriors", "vft_set_approx_ml", "vft_get_approx_ml", "vft_set_parents",
+    "vft_set_distance_matrix", "vft_set_transition_matrix", "vft_set_rates", "vft_set_ml_limits", "vft_set_jc_exact", "vft_set_near_posteriors", "vft_set_approx_ml", "vft_get_approx_ml", "vft_set_raw_distances", "vft_get_raw_distances", "vft_set_parents",
     "vft_set_node_scalars", "vft_get_node_scalars", "vft_set_out_distances", "vft_get_out_distances", "vft_out_distance_mirror", "vft_set_max_node",
     "vft_profile_upload", "vft_profile_download", "vft_profile_nvectors", "vft_average_profiles", "vft_out_profile_full", "vft_out_profile_partial", "vft_out_profile_finish",
     "vft_out_profile_update", "vft_out_profile_upload", "vft_out_profile_download", "vft_out_distances", "vft_sweep",
@@ -57,7 +57,7 @@ HIT_F64 = np.dtype([("j", np.int64), ("dist", np.float64), ("weight", np.float64
 
 HOST_LIB_PATH = os.path.join(LIB_DIR, "libvft_host.so")
 HOST_EXPORTS = ["vft_nj_run", "vft_nj_newick", "vft_nj_ml_newick", "vft_nj_last_join_crcs", "vft_nj_last_stage_seconds", "vft_nj_last_walk_dual", "vft_nj_last_lane_exchange", "vft_nj_lane_share", "vft_nj_out_profile_block", "vft_nj_last_gamma", "vft_nj_round_plan", "vft_nj_make_matrix", "vft_nj_set_log", "vft_nj_get_log", "vft_tree_partitioning", "vft_knuth_stream", "vft_ml_lengths", "vft_gtr_tables",
-                "vft_aa_model_tables", "vft_aa_near_tables", "vft_blosum45_tables", "vft_aa_model_as_distance_tables"]
+                "vft_aa_model_tables", "vft_aa_near_tables", "vft_nj_set_aa_transition", "vft_nj_get_aa_transition", "vft_aa_model_matrix", "vft_aa_tables_from_matrix", "vft_aa_near_tables_from_matrix", "vft_blosum45_tables", "vft_aa_model_as_distance_tables"]
 
 
 class _NJOptions(C.Structure):
@@ -87,7 +87,7 @@ def load_host_library():
     return _host_lib
 
 
-AA_MODELS = {None: 0, "": 0, "jtt": 1, "wag": 2, "lg": 3}
+AA_MODELS = {None: 0, "": 0, "jtt": 1, "wag": 2, "lg": 3, "custom": 4}   # custom: `-trans`, the matrix set with set_aa_transition
 # vft_nj_options as the reference's Options start out (include/vft_host.h); every member not named here starts at zero
 NJ_DEFAULTS = dict(tophits_mult=1.0, tophits_close=-1.0, topvisible_mult=1.5, stale_out_limit=0.01, f_reset_out_profile=0.02, n_reset_out_profile=200,
                    tophits2_safety=3, tophits2_mult=1.0, tophits2_refresh=0.6, threads=1, ml_accuracy=1)
@@ -325,12 +325,17 @@ def logging_to(log):
 def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtype=np.float32, me_lengths=False,
               unique=None, scoredist=False, n_bootstrap=0, mllen=0, return_loglk=False, return_rates=False, me_nni=False, ml_nni=0, spr=0, gtr=False, return_gtr=False,
               aa_model=None, comm=None, threads=1, debug_flags=0, gamma=False, out_profile_parts=0, slow=False, intree=None, pseudo=0.0,
-              ml_accuracy=1, slow_nni=False, nni_rounds=None, ml_nni_rounds=None, spr_length=None, approx_ml=False, log=None):
+              ml_accuracy=1, slow_nni=False, nni_rounds=None, ml_nni_rounds=None, spr_length=None, approx_ml=False, log=None, rawdist=False,
+              aa_trans=None):
     """The NJ phase of the whole alignment `codes_all` (duplicates included) as the reference's "NJ" tree string.
     log (path or open descriptor): `-log FILE` - the reference's log lines of this run, written as its stages finish (vft_nj_set_log;
     README "-log"); a path is created or truncated.  None = no log, and nothing is recorded.
     approx_ml: `-approxml` - the ML stages' posteriors of a protein run take the near-constant approximation where it holds; no member
     of vft_nj_options but state of the context: ops.set_approx_ml(True) on what make_ops returns, before the driver runs.
+    rawdist: `-rawdist` - the minimum-evolution stages (NNIs, SPR chains, their branch lengths, the local-bootstrap supports) compare
+    uncorrected distances; state of the context like approx_ml: ops.set_raw_distances(True) on what make_ops returns.
+    aa_trans: `-trans FILE` - the file's text (str / bytes), or (matrix[20,20], stat[20]); the ML stages run under that model whatever
+    aa_model says (the reference ignores -wag / -lg beside -trans).  Process state for the length of the call (set_aa_transition).
     intree (str): `-intree` - Newick text of a starting tree; the NJ phase does not run (vft_nj_options.intree).
     pseudo (float): `-pseudo W` - pseudocount distances in the minimum-evolution stages, 0 = off (vft_nj_options.pseudo_weight).
     ml_accuracy (int): `-mlacc N`; slow_nni: `-slownni`; nni_rounds / ml_nni_rounds (int > 0): `-nni N` / `-mlnni N` (0 rounds are
@@ -350,6 +355,12 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
     ops = make_ops(n, L)
     if approx_ml:
         ops.set_approx_ml(True)
+    if rawdist:
+        ops.set_raw_distances(True)
+    if aa_trans is not None:
+        if ops.n_codes != 20:   # (VeryFastTree.cpp:100)
+            raise VftError("aa_trans (-trans) is an amino-acid model: the alignment holds nucleotides")
+        aa_model = "custom"
     me_nni, spr, ml_nni = zero_round_stages(me_nni, spr, ml_nni, nni_rounds, ml_nni_rounds)
     opt = _nj_options(fastest=fastest, use_tophits_2nd=second_level, scoredist=scoredist, mllen=mllen, me_nni=me_nni, ml_nni=ml_nni, spr=spr, gtr=gtr,
                       aa_model=aa_model, comm=comm, threads=threads, debug_flags=debug_flags, gamma=gamma, out_profile_parts=out_profile_parts, slow=slow,
@@ -366,7 +377,7 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
     n_rates = I32(0)
     ratecat = np.zeros(L, np.int32)
     gtr_out = np.zeros(10, np.float64)
-    with logging_to(log):
+    with logging_to(log), aa_transition(aa_trans):
         rc = lib.vft_nj_ml_newick(ops.ctx, _ptr(codes), I64(n), I64(L), I32(np.dtype(dtype).itemsize), C.byref(opt),
                                   I32(1 if me_lengths else 0), I32(n_bootstrap), _ptr(unique_first), _ptr(aln_next),
                                   I64(len(codes_all)), blob, out, I64(cap), C.byref(olen), _ptr(loglk), I32(64),
@@ -380,6 +391,81 @@ def nj_newick(make_ops, codes_all, names, fastest=False, second_level=None, dtyp
     if return_loglk:
         return out.value.decode(), loglk[:n_rounds.value]
     return out.value.decode()
+
+
+def read_aa_transition(text):
+    """The parse of `-trans FILE` (vft_read_aa_transition, host/ReadTransition.h; no device): text = the file's text (str or bytes).
+    Returns (matrix[20,20], stat[20]); a VftError with the reference's message where the reference refuses the file."""
+    lib = load_host_library()
+    raw = text.encode() if isinstance(text, str) else bytes(text)
+    if b"\0" in raw:
+        raise VftError("aa_trans: the text holds a NUL character")
+    matrix, stat, err = np.zeros((20, 20)), np.zeros(20), C.create_string_buffer(512)
+    lib.vft_read_aa_transition.argtypes = [C.c_char_p, P, P, C.c_char_p, I32]
+    if lib.vft_read_aa_transition(raw, _ptr(matrix), _ptr(stat), err, 512) != 0:
+        raise VftError(err.value.decode() or "vft_read_aa_transition failed")
+    return matrix, stat
+
+
+def set_aa_transition(model=None):
+    """vft_nj_set_aa_transition: the matrix aa_model="custom" stands for in the tree runs of this process that follow - the text of a
+    `-trans` file or (matrix, stat); None clears it."""
+    lib = load_host_library()
+    lib.vft_nj_set_aa_transition.argtypes = [P, P]
+    if model is None:
+        lib.vft_nj_set_aa_transition(None, None)
+        return
+    matrix, stat = read_aa_transition(model) if isinstance(model, (str, bytes, bytearray)) else model
+    matrix, stat = np.ascontiguousarray(matrix, np.float64), np.ascontiguousarray(stat, np.float64)
+    if matrix.shape != (20, 20) or stat.shape != (20,):
+        raise VftError("aa_trans: a matrix of 20 x 20 rates and 20 stationary frequencies")
+    if lib.vft_nj_set_aa_transition(_ptr(matrix), _ptr(stat)) != 0:
+        raise VftError("vft_nj_set_aa_transition: positive frequencies and finite rates")
+
+
+@contextlib.contextmanager
+def aa_transition(model):
+    """for the block, aa_model="custom" is `model` (set_aa_transition); cleared behind the block, also after an error.  None: nothing."""
+    if model is None:
+        yield
+        return
+    set_aa_transition(model)
+    try:
+        yield
+    finally:
+        set_aa_transition(None)
+
+
+def aa_model_matrix(model):
+    """A built-in model's constants (vft_aa_model_matrix): (matrix[20,20], stat[20])."""
+    lib = load_host_library()
+    matrix, stat = np.zeros((20, 20)), np.zeros(20)
+    if lib.vft_aa_model_matrix(I32(AA_MODELS[model]), _ptr(matrix), _ptr(stat)) != 0:
+        raise VftError("vft_aa_model_matrix failed")
+    return matrix, stat
+
+
+def aa_tables_from_matrix(matrix, stat, dtype=np.float32):
+    """aa_model_tables for any rate matrix (vft_aa_tables_from_matrix; no device): the same dict."""
+    lib = load_host_library()
+    matrix, stat = np.ascontiguousarray(matrix, np.float64), np.ascontiguousarray(stat, np.float64)
+    out = dict(stat=np.zeros(20), statinv=np.zeros(20), eigenval=np.zeros(20), codefreq=np.zeros((21, 20)),
+               eigeninv=np.zeros((20, 20)), eigeninvT=np.zeros((20, 20)))
+    rc = lib.vft_aa_tables_from_matrix(_ptr(matrix), _ptr(stat), I32(np.dtype(dtype).itemsize), _ptr(out["stat"]), _ptr(out["statinv"]),
+                                       _ptr(out["eigenval"]), _ptr(out["codefreq"]), _ptr(out["eigeninv"]), _ptr(out["eigeninvT"]))
+    if rc != 0:
+        raise VftError("vft_aa_tables_from_matrix failed")
+    return out
+
+
+def aa_near_tables_from_matrix(matrix, stat, dtype=np.float32):
+    """aa_near_tables for any rate matrix (vft_aa_near_tables_from_matrix; no device): dict of nearP[20,20], nearFreq[20,20]."""
+    lib = load_host_library()
+    matrix, stat = np.ascontiguousarray(matrix, np.float64), np.ascontiguousarray(stat, np.float64)
+    out = dict(nearP=np.zeros((20, 20)), nearFreq=np.zeros((20, 20)))
+    if lib.vft_aa_near_tables_from_matrix(_ptr(matrix), _ptr(stat), I32(np.dtype(dtype).itemsize), _ptr(out["nearP"]), _ptr(out["nearFreq"])) != 0:
+        raise VftError("vft_aa_near_tables_from_matrix failed")
+    return out
 
 
 def round_plan(n_seqs, nni_rounds=None, ml_nni_rounds=None, spr=2):
@@ -637,6 +723,14 @@ class HipProfileOps:
 
     def get_approx_ml(self):
         return bool(self.lib.vft_get_approx_ml(self.ctx))
+
+    def set_raw_distances(self, on=True):
+        """`-rawdist` (vft_set_raw_distances): the supports and the walk server's dual commands compare uncorrected distances, and the
+        host driver's minimum-evolution stages do; off by default"""
+        self._chk(self.lib.vft_set_raw_distances(self.ctx, I32(1 if on else 0)))
+
+    def get_raw_distances(self):
+        return bool(self.lib.vft_get_raw_distances(self.ctx))
 
     def set_rates(self, rates, ratecat):
         rates = self.real(rates)

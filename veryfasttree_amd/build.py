@@ -23,7 +23,7 @@ FLAGS = BASE_FLAGS + EXTRA_FLAGS
 
 HOST_LIB = os.path.join(HERE, "lib", "libvft_host.so")
 HOST_SOURCES = [os.path.join(HERE, "host", "nj_driver.cpp")]
-HOST_DEPS = HOST_SOURCES + [os.path.join(HERE, "host", h) for h in ("NJDriver.h", "ReadTree.h", "SeqMatrix.h", "MLLengths.h", "PseudoDistances.h", "StageLog.h", "KnuthRng.h", "GtrModel.h", "AAModels.h", "AAModelData.h")] + \
+HOST_DEPS = HOST_SOURCES + [os.path.join(HERE, "host", h) for h in ("NJDriver.h", "ReadTree.h", "ReadTransition.h", "SeqMatrix.h", "MLLengths.h", "PseudoDistances.h", "StageLog.h", "KnuthRng.h", "GtrModel.h", "AAModels.h", "AAModelData.h")] + \
     [os.path.join(HERE, "..", "include", "vft_host.h"), os.path.join(HERE, "..", "include", "vft_hip.h")]
 
 

@@ -124,6 +124,7 @@ struct vft_ctx {
     void *nearTab[2] = {nullptr, nullptr};   // vft_set_near_posteriors: nearP, nearFreq of the transition matrix set last
     bool hasNear = false;
     bool approxML = false;                // vft_set_approx_ml
+    bool rawDistances = false;            // vft_set_raw_distances (`-rawdist`): no logCorrect in the supports, nor in the walk server's comparison
     void *rates = nullptr;
     int32_t *ratecat = nullptr;
     int32_t nRates = 0;
@@ -907,6 +908,17 @@ extern "C" int vft_set_approx_ml(vft_ctx *c, int32_t on) {
 
 extern "C" int vft_get_approx_ml(vft_ctx *c) { return c && c->approxML ? 1 : 0; }
 
+// `-rawdist` (Options::logdist = false): the minimum-evolution stages compare uncorrected profile distances.  State of the context,
+// off by default, read where this library log-corrects: vft_split_supports (the third flavour of vft_support_decide and of the host's
+// near-tie decisions) and every command of the walk server (VFT_WS_RAW_BIT).
+extern "C" int vft_set_raw_distances(vft_ctx *c, int32_t on) {
+    if (!c) return VFT_ERR_INVALID;
+    c->rawDistances = on != 0;
+    return VFT_OK;
+}
+
+extern "C" int vft_get_raw_distances(vft_ctx *c) { return c && c->rawDistances ? 1 : 0; }
+
 // -approxml without its tables is an error, not the exact posterior under another name
 static int approx_ok(vft_ctx *c) {
     if (c->approxML && c->d.nCodes == 20 && c->hasTm && !c->hasNear)
@@ -1509,7 +1521,7 @@ static int ws_command(vft_ctx *c, int32_t nOps, const int64_t *out, const int64_
     }
     c->ws.wantWeight[seq % VFT_WS_RING] = q && weights;
     ws_put(c, seq, 0, VFT_WS_CMD_WORK | ((uint32_t) nOps << 8) | (q ? 1u << 16 : 0u) | (noWait ? 1u << 17 : 0u) | (c->ws.scoredist ? 1u << 21 : 0u) |
-                      (q && weights ? 1u << VFT_WS_WEIGHT_BIT : 0u));
+                      (q && weights ? 1u << VFT_WS_WEIGHT_BIT : 0u) | (c->rawDistances ? 1u << VFT_WS_RAW_BIT : 0u));
     if (c->ws.mailOnDevice) __builtin_ia32_sfence();
     *seqOut = seq;
     return VFT_OK;
@@ -1668,7 +1680,7 @@ extern "C" int vft_walk_submit_dual(vft_ctx *c, int32_t n0, const int64_t *out0,
     }
     // (bit 17 - "no workgroup is still reading rows" - stays clear: the step before is running)
     ws_put(c, seq, 0, VFT_WS_CMD_WORK | ((uint32_t) n0 << 8) | (1u << VFT_WS_DUAL_BIT) | (q0 ? 0u : 1u << 19) | (q1 ? 0u : 1u << 20) |
-                      (scoredist ? 1u << 21 : 0u) | ((uint32_t) n1 << 24));
+                      (scoredist ? 1u << 21 : 0u) | (c->rawDistances ? 1u << VFT_WS_RAW_BIT : 0u) | ((uint32_t) n1 << 24));
     if (c->ws.mailOnDevice) __builtin_ia32_sfence();
     *ticket = seq;
     return VFT_OK;
@@ -4462,7 +4474,8 @@ extern "C" int vft_split_supports(vft_ctx *c, int64_t n, const int64_t *a, const
     VFTCHK(st.put(oCol, colT.data(), colT.size() * 4));
     unsigned int *dCnt = st.dev<unsigned int>(oCnt), *dNFlag = st.dev<unsigned int>(oNFlag);
     double *dFlag = st.dev<double>(oFlag);
-    const int32_t scoredist = (c->cfg.n_codes == 4 && !c->hasDm) ? 0 : 1;   // logCorrect's choice, NJ.tcc:324
+    // logCorrect's choice, NJ.tcc:324 - or none at all under `-rawdist` (vft_set_raw_distances; splitSupport's `if (options.logdist)`, NJ.tcc:660, :692)
+    const int32_t flavour = c->rawDistances ? VFT_SUPPORT_RAW : (c->cfg.n_codes == 4 && !c->hasDm) ? VFT_SUPPORT_JC : VFT_SUPPORT_SCOREDIST;
     // margins below eps are decided on the host with its own libm (the device's log may differ in the last bit);
     // a distance is < 3, so errors of a few 1e-16 cannot reach 1e-9
     const double eps = 1e-9;
@@ -4488,7 +4501,7 @@ extern "C" int vft_split_supports(vft_ctx *c, int64_t n, const int64_t *a, const
 #define VFT_SUPPORT_LAUNCH(KERNEL, WG)                                                                                        \
     launch((KERNEL), dim3((unsigned) m), dim3(WG), lds, c->stream, arena<REAL>(c), st.dev<const int64_t>(oA),                  \
            st.dev<const int64_t>(oB), st.dev<const int64_t>(oC), st.dev<const int64_t>(oD), m,                                 \
-           st.dev<const int32_t>(oCol), nBoot, scoredist, eps, dCnt, dNFlag, dFlag, flagCap)
+           st.dev<const int32_t>(oCol), nBoot, flavour, eps, dCnt, dNFlag, dFlag, flagCap)
         VFT_DISPATCH(c, {
             if (pairs == 3) VFT_SUPPORT_LAUNCH((k_split_support_long<REAL, NC, 3>), VFT_SUPPORT_LONG_WG);
             else if (pairs == 2) VFT_SUPPORT_LAUNCH((k_split_support_long<REAL, NC, 2>), VFT_SUPPORT_LONG_WG);
@@ -4508,9 +4521,13 @@ extern "C" int vft_split_supports(vft_ctx *c, int64_t n, const int64_t *a, const
             for (unsigned int f = 0; f < nFlag; f++) {
                 const double *r = &rec[(size_t) f * VFT_SUPPORT_REC];
                 double dd[6];
-                for (int j = 0; j < 6; j++) {   // logCorrect (NJ.tcc:322-330) with the host's log
+                for (int j = 0; j < 6; j++) {   // logCorrect (NJ.tcc:322-330) with the host's log; none of it under `-rawdist`
                     double x = r[1 + j];
-                    if (scoredist) x = x < 0.99 ? -1.3 * std::log(1.0 - x) : 3.0;
+                    if (flavour == VFT_SUPPORT_RAW) {
+                        dd[j] = x;
+                        continue;
+                    }
+                    if (flavour == VFT_SUPPORT_SCOREDIST) x = x < 0.99 ? -1.3 * std::log(1.0 - x) : 3.0;
                     else x = x < 0.74 ? -0.75 * std::log(1.0 - x * 4.0 / 3.0) : 3.0;
                     dd[j] = x < 3.0 ? x : 3.0;
                 }

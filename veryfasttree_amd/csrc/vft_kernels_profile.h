@@ -969,19 +969,24 @@ __global__ __launch_bounds__(OpThreads<NC>::value) void k_outprofile_chain(Arena
 // equal the reference's exactly.  counts[k] = resamples decided "supported" on the device.
 #define VFT_SUPPORT_WG 256
 #define VFT_SUPPORT_REC 7   // doubles per flagged record
+// what a resample's six distances go through before they are compared (`flavour`): logCorrect's Jukes-Cantor or scoredist-like
+// formula (NJ.tcc:322-330), or nothing at all - `-rawdist`, the reference's `if (options.logdist)` around both (NJ.tcc:660, :692)
+#define VFT_SUPPORT_JC 0
+#define VFT_SUPPORT_SCOREDIST 1
+#define VFT_SUPPORT_RAW 2
 
 // One resample's decision from its six uncorrected distances raw[j] = totw > 0.01 ? totp / totw : 3.0 (qAB, qAC, qAD, qBC,
 // qBD, qCD): true = supported, decided here; a near-tie goes to `flagged` for the host and counts as not decided.
 // Shared by k_split_support and k_split_support_long, so that both hand the host the same records.
-__device__ __forceinline__ bool vft_support_decide(const double (&raw)[6], int64_t k, int32_t scoredist, double eps,
+__device__ __forceinline__ bool vft_support_decide(const double (&raw)[6], int64_t k, int32_t flavour, double eps,
                                                    unsigned int *nFlagged, double *flagged, unsigned int flagCap) {
     double d[6];
 #pragma unroll
     for (int j = 0; j < 6; j++) {
         double x = raw[j];
-        // logCorrect, NJ.tcc:322-330
-        if (scoredist) x = x < 0.99 ? -1.3 * log(1.0 - x) : 3.0;
-        else x = x < 0.74 ? -0.75 * log(1.0 - x * 4.0 / 3.0) : 3.0;
+        // logCorrect, NJ.tcc:322-330 (an uncorrected distance is at most 3 already: the cap leaves it alone)
+        if (flavour == VFT_SUPPORT_SCOREDIST) x = x < 0.99 ? -1.3 * log(1.0 - x) : 3.0;
+        else if (flavour == VFT_SUPPORT_JC) x = x < 0.74 ? -0.75 * log(1.0 - x * 4.0 / 3.0) : 3.0;
         d[j] = x < 3.0 ? x : 3.0;
     }
     const double support1 = d[1] + d[4] - d[0] - d[5];   // AC + BD - AB - CD
@@ -1002,7 +1007,7 @@ __device__ __forceinline__ bool vft_support_decide(const double (&raw)[6], int64
 template <typename REAL, int NC>
 __global__ __launch_bounds__(VFT_SUPPORT_WG) void k_split_support(Arena<REAL> A, const int64_t *nA, const int64_t *nB,
                                                                   const int64_t *nC, const int64_t *nD, int64_t n,
-                                                                  const int32_t *colT, int32_t nBoot, int32_t scoredist,
+                                                                  const int32_t *colT, int32_t nBoot, int32_t flavour,
                                                                   double eps, unsigned int *counts,
                                                                   unsigned int *nFlagged, double *flagged,
                                                                   unsigned int flagCap) {
@@ -1043,7 +1048,7 @@ __global__ __launch_bounds__(VFT_SUPPORT_WG) void k_split_support(Arena<REAL> A,
         double raw[6];
 #pragma unroll
         for (int j = 0; j < 6; j++) raw[j] = totw[j] > 0.01 ? totp[j] / totw[j] : 3.0;
-        if (vft_support_decide(raw, k, scoredist, eps, nFlagged, flagged, flagCap)) atomicAdd(&nSupport, 1u);
+        if (vft_support_decide(raw, k, flavour, eps, nFlagged, flagged, flagCap)) atomicAdd(&nSupport, 1u);
     }
     __syncthreads();
     if (threadIdx.x == 0) counts[k] = nSupport;
@@ -1060,7 +1065,7 @@ __global__ __launch_bounds__(VFT_SUPPORT_WG) void k_split_support(Arena<REAL> A,
 template <typename REAL, int NC, int P>
 __global__ __launch_bounds__(VFT_SUPPORT_LONG_WG) void k_split_support_long(Arena<REAL> A, const int64_t *nA, const int64_t *nB,
                                                                             const int64_t *nC, const int64_t *nD, int64_t n,
-                                                                            const int32_t *colT, int32_t nBoot, int32_t scoredist,
+                                                                            const int32_t *colT, int32_t nBoot, int32_t flavour,
                                                                             double eps, unsigned int *counts,
                                                                             unsigned int *nFlagged, double *flagged,
                                                                             unsigned int flagCap) {
@@ -1155,7 +1160,7 @@ __global__ __launch_bounds__(VFT_SUPPORT_LONG_WG) void k_split_support_long(Aren
                 }
             }
         }
-        const bool sup = mine && vft_support_decide(raw, k, scoredist, eps, nFlagged, flagged, flagCap);
+        const bool sup = mine && vft_support_decide(raw, k, flavour, eps, nFlagged, flagged, flagCap);
         nSupport += (unsigned int) __popcll(__ballot(sup));
     }
     if ((threadIdx.x & 63) == 0 && nSupport) atomicAdd(&counts[k], nSupport);

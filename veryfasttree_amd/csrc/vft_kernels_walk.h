@@ -44,7 +44,7 @@
 // their alternative without a host round trip.  Header: bit 18 = dual, bits 8-15 = averages of alternative 0 (B and C swapped:
 // criteria[1] < criteria[2]), bits 24-31 = averages of alternative 1, bit 19 / 20 = alternative 0 / 1 is NOT a device step (the chain
 // ends there, the quartet is answered from the host's memo table, too many averages): the command then counts as an empty one;
-// bit 21 = logCorrect's scoredist flavour (NJ.tcc:322-330).
+// bit 21 = logCorrect's scoredist flavour (NJ.tcc:322-330); bit 23 = no logCorrect at all (VFT_WS_RAW_BIT below).
 // Granules: [0] header, [1..4] quartet 0, [5 .. 5 + 3 n0) averages 0, then quartet 1 (4) and averages 1 (3 n1): n0 + n1 <= 18.
 #define VFT_WS_DUAL_BIT 18
 #define VFT_WS_DUAL_MAXOPS 18
@@ -54,6 +54,13 @@
 // granules at the same indices, nothing else stored or waited for.  Dual commands never carry it (the comparison on the device works on
 // log-corrected distances without pseudocounts: the host sends no dual commands while it wants weights).
 #define VFT_WS_WEIGHT_BIT 22
+// Bit 23 of every command's header, plain or dual (`-rawdist`, vft_set_raw_distances: correctedPairDistances without its final
+// `if (options.logdist)`, NJ.tcc:1484): the distance a workgroup hands to the others for a dual command's comparison is the answer
+// itself, widened to double - no logCorrect, no logarithm, no cap.  The comparison is the same six numbers.  With bit 21 it forms the
+// two-bit flavour of the correction (none set: Jukes-Cantor, 21: scoredist-like, 23: none; 23 wins over 21).  A command without the
+// bit is answered bit for bit as before: the bit is read in that one place and a dual command carries it over to the plain command
+// it becomes.  (Bits 24-31 are a dual command's second count: 23 was the last free one.)
+#define VFT_WS_RAW_BIT 23
 #define VFT_WS_RES_WEIGHT 16   // first weight granule of a result slot
 #define VFT_WS_RES_CHOICE 12   // result granule of a dual command: {seq, 1 | alternative << 1 | not-a-device-step << 2} (workgroup 0)
 #define VFT_WS_FLAG_DIST 16    // flags[16 + 16 * (seq & 1) + 2 w (+ 1)]: workgroup w's LOG-CORRECTED distance of command seq (a double), tagged low / high half
@@ -364,7 +371,7 @@ __global__ __launch_bounds__(VFT_WS_WG_OF(NC)) void k_walk_server(Arena<REAL> A,
                     const uint32_t v = src < VFT_WS_GRAN ? sCmd[src] : 0u;
                     if (lane < 4 + 3 * nAlt) sCmd[1 + lane] = v;   // (one wavefront: every lane has read before any lane writes)
                     if (lane == 0) {
-                        sCmd[0] = (hdr & 0xFFu) | ((uint32_t) nAlt << 8) | (skip ? 0u : 1u << 16) | (hdr & (1u << 17)) | (hdr & (1u << 21));
+                        sCmd[0] = (hdr & 0xFFu) | ((uint32_t) nAlt << 8) | (skip ? 0u : 1u << 16) | (hdr & (1u << 17)) | (hdr & (1u << 21)) | (hdr & (1u << VFT_WS_RAW_BIT));
                         if (w == 0)
                             __hip_atomic_store(S.res + (size_t) (seq % VFT_WS_RING) * VFT_WS_RESG + VFT_WS_RES_CHOICE,
                                                ((unsigned long long) seq << 32) | 1ull | ((unsigned long long) alt << 1) | ((unsigned long long) (skip ? 1 : 0) << 2),
@@ -526,7 +533,7 @@ __global__ __launch_bounds__(VFT_WS_WG_OF(NC)) void k_walk_server(Arena<REAL> A,
         }
         if (threadIdx.x == 0) {
             // ... and, log-corrected (logCorrect, NJ.tcc:322-330; host/MLLengths.h: Jukes-Cantor or scoredist-like by bit 21 of the command,
-            // capped at 3; glibc's log bit for bit, vft_glibc_log.h), to the other workgroups: a dual command that follows compares the six
+            // capped at 3; glibc's log bit for bit, vft_glibc_log.h; as it is with VFT_WS_RAW_BIT), to the other workgroups: a dual command that follows compares the six
             // numbers on the device.  After the answer has gone out - the host does not wait for this - and one logarithm per workgroup,
             // side by side, instead of six in front of the next step's chain.
             const double top = sSum[0], denom = sSum[1];
@@ -536,6 +543,7 @@ __global__ __launch_bounds__(VFT_WS_WG_OF(NC)) void k_walk_server(Arena<REAL> A,
             if (!((hdr >> 21) & 1u)) x = dd < 0.74 ? -0.75 * vft_glibc_log(1.0 - dd * 4.0 / 3.0) : maxscore;
             else x = dd < 0.99 ? -1.3 * vft_glibc_log(1.0 - dd) : maxscore;
             x = x < maxscore ? x : maxscore;
+            if ((hdr >> VFT_WS_RAW_BIT) & 1u) x = dd;
             unsigned long long *dw = S.flags + VFT_WS_FLAG_DIST + 16 * (seq & 1u) + 2 * w;
             __hip_atomic_store(dw, ((unsigned long long) seq << 32) | (unsigned long long) (unsigned) __double2loint(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(dw + 1, ((unsigned long long) seq << 32) | (unsigned long long) (unsigned) __double2hiint(x), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

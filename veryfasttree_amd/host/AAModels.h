@@ -17,19 +17,23 @@ namespace veryfasttree {
     enum AAModel {
         AA_MODEL_JTT = 1,   /* the reference's default for amino acids (VeryFastTreeImpl.tcc:104-106) */
         AA_MODEL_WAG = 2,   /* -wag */
-        AA_MODEL_LG = 3     /* -lg */
+        AA_MODEL_LG = 3,    /* -lg */
+        AA_MODEL_CUSTOM = 4 /* -trans FILE: the matrix that was set (customAATransition below) */
     };
 
-    typedef TransitionTables<20> TransitionTables20;
-
-    /* what vft_set_distance_matrix takes: numeric_t values held in double */
-    struct DistanceTables20 {
-        double distances[20][20], codeFreq[20][20], eigenval[20], eigentot[20];
+    /* `-trans`: the user's rate matrix and stationary frequencies (host/ReadTransition.h), process state like the log's descriptor:
+       set by vft_nj_set_aa_transition, read by createAAModel(AA_MODEL_CUSTOM), cleared by the same call with NULL - never by a run */
+    struct AATransition {
+        bool set;
+        double matrix[20][20], stat[20];
     };
+    inline AATransition &customAATransition() {
+        static AATransition custom = {false, {{0}}, {0}};
+        return custom;
+    }
 
-    template<typename REAL>
-    inline void createAAModel(int model, TransitionTables20 &t) {
-        const double *stat, *flat;
+    /* a built-in model's constants as they stand in AAModelData.h (vft_aa_model_matrix) */
+    inline void aaModelConstants(int model, const double *&stat, const double *&flat) {
         switch (model) {
             case AA_MODEL_JTT:
                 stat = aa_data::kStatJTT92;
@@ -46,6 +50,25 @@ namespace veryfasttree {
             default:
                 throw std::invalid_argument("unknown amino-acid model (1 = JTT, 2 = WAG, 3 = LG)");
         }
+    }
+
+    typedef TransitionTables<20> TransitionTables20;
+
+    /* what vft_set_distance_matrix takes: numeric_t values held in double */
+    struct DistanceTables20 {
+        double distances[20][20], codeFreq[20][20], eigenval[20], eigentot[20];
+    };
+
+    template<typename REAL>
+    inline void createAAModel(int model, TransitionTables20 &t) {
+        if (model == AA_MODEL_CUSTOM) {
+            const AATransition &custom = customAATransition();
+            if (!custom.set) throw std::invalid_argument("amino-acid model 4 (-trans) without a matrix: vft_nj_set_aa_transition comes first");
+            createTransitionTables<REAL, 20>(custom.matrix, custom.stat, t);
+            return;
+        }
+        const double *stat, *flat;
+        aaModelConstants(model, stat, flat);
         double matrix[20][20];
         for (int i = 0; i < 20; i++)
             for (int j = 0; j < 20; j++) matrix[i][j] = flat[20 * i + j];

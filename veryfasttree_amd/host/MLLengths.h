@@ -631,7 +631,7 @@ namespace veryfasttree {
 
         struct NNIParams {
             bool useML = false;
-            bool scoredist = false;      /* logCorrect flavour of the ME criterion (NJ.tcc:322-330) */
+            int correction = DIST_JUKES_CANTOR;   /* what the ME criterion's distances go through (host/PseudoDistances.h: DistCorrection) */
             double ftol = 0.001, atol = 1e-4, minDelta = 1.0e-4 /* MEMinDelta */;
             int32_t mlAccuracy = 1;      /* `-mlacc N`: rounds per quartet (at least 2); from 2 on no alternative is dropped (NJ.tcc:4893, :4957) */
             bool fastNNI = true;         /* false = `-slownni`: no subtree is skipped (NJ.tcc:6049) */
@@ -686,7 +686,7 @@ namespace veryfasttree {
                     if (r.star) nStarTests++;
                 } else {
                     int64_t qq[4];
-                    meCriteria(node, prm.scoredist, upHave, qq, criteria);
+                    meCriteria(node, prm.correction, upHave, qq, criteria);
                     if (criteria[1] < criteria[0] && criteria[1] <= criteria[2]) choice = 1;
                     else if (criteria[2] < criteria[0] && criteria[2] <= criteria[1]) choice = 2;
                     for (int i = 0; i < 3; i++) criteria[i] = -criteria[i];   /* higher is better, as for ML */
@@ -888,7 +888,7 @@ namespace veryfasttree {
                         if (res[t].star) nStarTests++;
                     } else {
                         double c[6];
-                        pseudoDistancesOfDevice<REAL>(6, d.data() + 6 * t, w.data() + 6 * t, pseudoWeight, prm.scoredist, c);
+                        pseudoDistancesOfDevice<REAL>(6, d.data() + 6 * t, w.data() + 6 * t, pseudoWeight, prm.correction, c);
                         criteria[0] = c[0] + c[5];
                         criteria[1] = c[1] + c[4];
                         criteria[2] = c[2] + c[3];
@@ -1005,7 +1005,7 @@ namespace veryfasttree {
 
         /* one node of traverseSPR (NJ.tcc:6213-6300): its up to four chains of forced minimum-evolution NNIs, best prefix kept, rest
            unwound; true when the tree changed */
-        bool sprAttempt(int64_t node, bool scoredist, int maxSPRLength, std::vector<char> &upHave) {
+        bool sprAttempt(int64_t node, int correction, int maxSPRLength, std::vector<char> &upHave) {
             if (node == root) return false;
             struct Step {
                 int64_t nodes[2];
@@ -1060,10 +1060,10 @@ namespace veryfasttree {
                         if (chainLength >= 1 && walkDual && serverUp && tk.pending) {
                             if (walkStats) {
                                 const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-                                dualSent = specContinuations(node, around, q, (int) chainLength, maxSPRLength, scoredist, upHave);
+                                dualSent = specContinuations(node, around, q, (int) chainLength, maxSPRLength, correction, upHave);
                                 walkSpecSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
                             } else
-                            dualSent = specContinuations(node, around, q, (int) chainLength, maxSPRLength, scoredist, upHave);
+                            dualSent = specContinuations(node, around, q, (int) chainLength, maxSPRLength, correction, upHave);
                         }
                         if (chainLength == 0) {
                             swapBC = acFirst != 0;
@@ -1072,11 +1072,11 @@ namespace veryfasttree {
                         } else {
                             if (firstOpen) {
                                 double c0[3];
-                                meCollect(first, scoredist, c0);
+                                meCollect(first, correction, c0);
                                 steps[0].deltaLength = (steps[0].bc ? c0[1] : c0[2]) - c0[0];
                                 firstOpen = false;
                             }
-                            meCollect(tk, scoredist, criteria);
+                            meCollect(tk, correction, criteria);
                             if (verifyDual) {   /* the workgroups made the same comparison on the same six numbers */
                                 int32_t alt = -1, skipped = -1;
                                 chk(vft_walk_dual_choice(ctx, tk.ticket, &alt, &skipped));
@@ -1118,12 +1118,12 @@ namespace veryfasttree {
                         tk.pending = true;
                         tk.ticket = adopted.ticket;
                         double c[3];
-                        meCollect(tk, scoredist, c);
+                        meCollect(tk, correction, c);
                         throw std::logic_error("MLLengths::sprAttempt: a continuation was adopted beyond the chain's end");
                     }
                     if (firstOpen) {
                         double c0[3];
-                        meCollect(first, scoredist, c0);
+                        meCollect(first, correction, c0);
                         steps[0].deltaLength = (steps[0].bc ? c0[1] : c0[2]) - c0[0];
                     }
                     double dMinDelta = 0.0, dTotDelta = 0.0;
@@ -1156,7 +1156,7 @@ namespace veryfasttree {
            maxSPRLength minimum-evolution NNIs around its parent and its sibling (findSPRSteps, NJ.tcc:1805-1859; the
            first step forced to AC or AD), keeping the prefix of the chain with the best total length change and
            unwinding the rest (unwindSPRStep, NJ.tcc:1861-1879).  Returns the number of accepted moves. */
-        int64_t doSPR(bool scoredist, int maxSPRLength = 10) {
+        int64_t doSPR(int correction, int maxSPRLength = 10) {
             if (nSeqs <= 3 || maxSPRLength < 1) return 0;
             std::vector<char> traversal((size_t) nNodes, 0), upHave((size_t) nNodes, 0);
             std::vector<int64_t> nodeList;
@@ -1167,11 +1167,11 @@ namespace veryfasttree {
             }
             int64_t nSPR = 0;
             WalkServerGuard server(*this);
-            if (serverUp) chk(vft_walk_scoredist(ctx, scoredist ? 1 : 0));
+            if (serverUp) chk(vft_walk_scoredist(ctx, correction == DIST_SCOREDIST ? 1 : 0));
             static const bool stageTrace = std::getenv("VFT_STAGE_TRACE") != nullptr;
             int64_t nDone = 0;
             for (int64_t node: nodeList) {
-                if (sprAttempt(node, scoredist, maxSPRLength, upHave)) nSPR++;
+                if (sprAttempt(node, correction, maxSPRLength, upHave)) nSPR++;
                 if (stageTrace && (++nDone % 100000) == 0) fprintf(stderr, "[stage]   SPR: %lld of %zu nodes, %lld steps, %lld moves\n", (long long) nDone, nodeList.size(), (long long) sprSteps, (long long) nSPR);
             }
             server.finish();
@@ -1673,12 +1673,7 @@ namespace veryfasttree {
         int64_t splits() const { return (int64_t) order.size(); }
 
     private:
-        static double logCorrect(double dist, bool scoredist) {   /* NJ.tcc:322-330 */
-            const double maxscore = 3.0;
-            if (!scoredist) dist = dist < 0.74 ? -0.75 * std::log(1.0 - dist * 4.0 / 3.0) : maxscore;
-            else dist = dist < 0.99 ? -1.3 * std::log(1.0 - dist) : maxscore;
-            return dist < maxscore ? dist : maxscore;
-        }
+        static double logCorrect(double dist, int correction) { return pseudoLogCorrect(dist, correction); }   /* NJ.tcc:322-330 */
 
         int64_t siblingOf(int64_t v) const {   /* NJ.tcc:1977-1990: not defined below the root */
             const int64_t p = parent[(size_t) v];
@@ -1869,7 +1864,7 @@ namespace veryfasttree {
             WalkTxnLog log;
         };
         SprAlt specAlt[2];
-        bool specContinuations(int64_t node, int64_t around, const int64_t q[4], int chainLength, int maxSPRLength, bool scoredist, std::vector<char> &upHave) {
+        bool specContinuations(int64_t node, int64_t around, const int64_t q[4], int chainLength, int maxSPRLength, int correction, std::vector<char> &upHave) {
             for (int alt = 0; alt < 2; alt++) {
                 SprAlt &A = specAlt[alt];
                 A.valid = false;
@@ -1900,7 +1895,7 @@ namespace veryfasttree {
             uint32_t ticket = 0;
             const SprAlt &A0 = specAlt[0], &A1 = specAlt[1];
             chk(vft_walk_submit_dual(ctx, (int32_t) A0.out.size(), A0.out.data(), A0.a.data(), A0.b.data(), A0.valid ? A0.q4 : nullptr,
-                                     (int32_t) A1.out.size(), A1.out.data(), A1.a.data(), A1.b.data(), A1.valid ? A1.q4 : nullptr, scoredist ? 1 : 0, &ticket));
+                                     (int32_t) A1.out.size(), A1.out.data(), A1.a.data(), A1.b.data(), A1.valid ? A1.q4 : nullptr, correction == DIST_SCOREDIST ? 1 : 0, &ticket));
             specAlt[0].ticket = specAlt[1].ticket = ticket;
             walkDualSent++;
             return true;
@@ -1975,7 +1970,7 @@ namespace veryfasttree {
                 chk(vft_profile_distances(ctx, 6, pi, pj, t.d, t.w));
             }
         }
-        void meCollect(MeTicket &t, bool scoredist, double criteria[3]) {
+        void meCollect(MeTicket &t, int correction, double criteria[3]) {
             if (t.pending) {
                 const bool withWeights = pseudoWeight > 0;   /* (submitted with vft_walk_submit_w: meSubmit) */
                 if (walkStats) {
@@ -1996,15 +1991,15 @@ namespace veryfasttree {
                 t.keyed = false;
             }
             double c[6];
-            pseudoDistancesOfDevice<REAL>(6, t.d, t.w, pseudoWeight, scoredist, c);
+            pseudoDistancesOfDevice<REAL>(6, t.d, t.w, pseudoWeight, correction, c);
             criteria[0] = c[0] + c[5];
             criteria[1] = c[1] + c[4];
             criteria[2] = c[2] + c[3];
         }
-        void meCriteria(int64_t node, bool scoredist, std::vector<char> &upHave, int64_t q[4], double criteria[3]) {
+        void meCriteria(int64_t node, int correction, std::vector<char> &upHave, int64_t q[4], double criteria[3]) {
             MeTicket t;
             meSubmit(node, upHave, q, t);
-            meCollect(t, scoredist, criteria);
+            meCollect(t, correction, criteria);
         }
 
         /* traversePostorder (NJ.tcc:3343-3380) on the tree as it is now */

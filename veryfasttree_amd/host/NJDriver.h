@@ -154,6 +154,7 @@ namespace veryfasttree {
                 }
                 selfweightLeaf[i] = (REAL) c;
             }
+            correction = distCorrectionOf(vft_get_raw_distances(ctx) != 0, this->opt.scoredist);
             if (opt.aaModel) installBlosum45();
             if (opt.comm && opt.comm->world > 1) {
                 if (!opt.comm->allgather || !opt.comm->d_send || !opt.comm->d_recv || !opt.comm->h_send || !opt.comm->h_recv)
@@ -713,7 +714,7 @@ namespace veryfasttree {
         }
 
         /* updateBranchLengths (NJ.tcc:6514-6595) on the finished NJ topology, as the pipeline does before it prints a
-           minimum-evolution tree (VeryFastTreeImpl.tcc:205-213): every branch length from log-corrected profile
+           minimum-evolution tree (VeryFastTreeImpl.tcc:205-213): every branch length from log-corrected (`-rawdist`: uncorrected) profile
            distances between the node's children / sibling / up-profile (correctedPairDistances NJ.tcc:1460-1488,
            logCorrect :322-330; -nj weighting; the pseudocounts of `-pseudo`
            when opt.pseudoWeight > 0, from the weights the same call returns - host/PseudoDistances.h).  The up-profile of an internal node X
@@ -792,10 +793,10 @@ namespace veryfasttree {
                 const int64_t f = firstPair[(size_t) v];
                 double d[6];
                 if (v < nSeqs) {
-                    pseudoDistancesOfDevice<REAL>(3, pd.data() + f, pw.data() + f, opt.pseudoWeight, opt.scoredist, d);   /* AB AC BC */
+                    pseudoDistancesOfDevice<REAL>(3, pd.data() + f, pw.data() + f, opt.pseudoWeight, correction, d);   /* AB AC BC */
                     branchlength[(size_t) v] = (REAL) ((d[0] + d[1] - d[2]) / 2.0);
                 } else {
-                    pseudoDistancesOfDevice<REAL>(6, pd.data() + f, pw.data() + f, opt.pseudoWeight, opt.scoredist, d);
+                    pseudoDistancesOfDevice<REAL>(6, pd.data() + f, pw.data() + f, opt.pseudoWeight, correction, d);
                     /* qAB 0, qAC 1, qAD 2, qBC 3, qBD 4, qCD 5 */
                     branchlength[(size_t) v] = (REAL) ((d[1] + d[2] + d[3] + d[4]) / 4.0 - (d[0] + d[5]) / 2.0);
                     if (log) {   /* testSplitsMinEvo (NJ.tcc:6660-6710, no constraints) reads the same six distances of the same quartet */
@@ -854,7 +855,7 @@ namespace veryfasttree {
             tree.comm = opt.comm;
             typename MLLengths<REAL>::NNIParams prm;
             prm.useML = false;
-            prm.scoredist = opt.scoredist;
+            prm.correction = correction;
             prm.fastNNI = !opt.slowNNI;
             std::vector<typename MLLengths<REAL>::NNIStats> stats;
             tree.initNNIStats(stats);
@@ -884,7 +885,7 @@ namespace veryfasttree {
                     {
                         const std::chrono::steady_clock::time_point ts = std::chrono::steady_clock::now();
                         if (std::getenv("VFT_STAGE_TRACE")) fprintf(stderr, "[stage] SPR round begins after %lld NNI rounds\n", (long long) (i + 1));
-                        meSPRs += tree.doSPR(opt.scoredist, opt.sprLength);
+                        meSPRs += tree.doSPR(correction, opt.sprLength);
                         meSPRSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
                         if (std::getenv("VFT_STAGE_TRACE")) fprintf(stderr, "[stage] SPR round done: %.1f s of SPR so far, %lld moves\n", meSPRSeconds, (long long) meSPRs);
                     }
@@ -900,7 +901,7 @@ namespace veryfasttree {
             }
             while (sprRemaining > 0) {
                 const std::chrono::steady_clock::time_point ts = std::chrono::steady_clock::now();
-                meSPRs += tree.doSPR(opt.scoredist, opt.sprLength);
+                meSPRs += tree.doSPR(correction, opt.sprLength);
                 meSPRSeconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - ts).count();
                 if (log) {   /* VeryFastTreeImpl.tcc:202 */
                     adoptTree(tree.parents(), tree.children());
@@ -918,6 +919,10 @@ namespace veryfasttree {
             return total;
         }
 
+        /* Jukes-Cantor, scoredist-like or - `-rawdist`, the context's vft_set_raw_distances - none (host/PseudoDistances.h): decided once,
+           in the constructor, for updateBranchLengths, the ME NNI criteria and the SPR chains (the supports and the walk server's own
+           comparison read the same switch inside the HIP library) */
+        int correction = DIST_JUKES_CANTOR;
         int64_t meSPRs = 0, meSPRSteps = 0;
         int64_t meSPRDualSent = 0, meSPRDualTaken = 0;   /* SPR chains: dual commands sent / continuations the walk server ran without waiting for the host */
         int64_t laneGathers = 0, laneGatherBytes = 0;   /* lanes across ranks: all-gathers of verdicts + lengths, bytes received */

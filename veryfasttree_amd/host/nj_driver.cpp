@@ -18,6 +18,7 @@
 #include "AAModels.h"
 #include "SeqMatrix.h"
 #include "ReadTree.h"
+#include "ReadTransition.h"
 #include "StageLog.h"
 
 // CRC-32 (the zlib polynomial) of the last join order this process produced, per chunk of joins: lets a caller that only asked
@@ -342,6 +343,14 @@ static void checkThorough(const vft_nj_options *o) {
         throw std::invalid_argument("vft_nj_options.spr_length (-sprlength) is above 64: the chain buffers of MLLengths::sprAttempt hold 64 steps");
 }
 
+/* `-trans`: the model "the matrix that was set" without one is refused before anything reaches the device - never a silent JTT run
+   (include/vft_host.h, vft_nj_set_aa_transition) */
+static void checkAAModel(const vft_nj_options *o) {
+    if (!o || o->aa_model != veryfasttree::AA_MODEL_CUSTOM) return;
+    if (!veryfasttree::customAATransition().set)
+        throw std::invalid_argument("vft_nj_options.aa_model = 4 (-trans) without a matrix: vft_nj_set_aa_transition comes first");
+}
+
 /* the rounds of the refinement stages (host/NJDriver.h meNNIRoundsToDo / mlNNIRoundsToDo / sprBehindNNIRound), pure host code */
 extern "C" int vft_nj_round_plan(int64_t nSeqs, int32_t nniRounds, int32_t mlNNIRounds, int32_t spr, int64_t *out, int64_t *sprBehind, int64_t cap) {
     if (nSeqs < 1 || nniRounds < 0 || mlNNIRounds < 0 || spr < 0 || !out) return VFT_ERR_INVALID;
@@ -379,6 +388,10 @@ static std::string runTree(vft_ctx *ctx, const uint8_t *codes, int64_t nSeqs, in
     veryfasttree::ReadTreeResult tree;
     if (o && o->intree) tree = readTreeText(o->intree, nAll, names, uniqueFirst, alnNext, nSeqs);
     /* the log opens behind every refusal - the option checks of the caller, the parse above: a run that is refused writes nothing */
+    if (o && o->aa_model == veryfasttree::AA_MODEL_CUSTOM) {   /* VeryFastTree.cpp:100 */
+        int32_t nCodes = 0;
+        if (vft_get_n_codes(ctx, &nCodes) != VFT_OK || nCodes != 20) throw std::invalid_argument("-trans is an amino-acid model: the context holds nucleotides");
+    }
     const std::unique_ptr<veryfasttree::StageLog> sink = openLog(o ? o->comm : nullptr);
     veryfasttree::StageLog *const log = sink.get();
     veryfasttree::NJDriver<REAL> drv(ctx, codes, nSeqs, nPos, toOptions(o));
@@ -481,6 +494,7 @@ extern "C" int vft_nj_ml_newick(vft_ctx *ctx, const uint8_t *codes, int64_t nSeq
         checkSlow(opt);
         checkPseudo(opt);
         checkThorough(opt);
+        checkAAModel(opt);
         std::vector<double> ll, rates;
         std::vector<int64_t> ratecat;
         const std::string t = precision == 8 ? runTree<double>(ctx, codes, nSeqs, nPos, opt, meLengths != 0, nBootstrap, uniqueFirst, alnNext, nAll, names, ll, rates, ratecat, gtrOut)
@@ -632,6 +646,102 @@ extern "C" int vft_aa_model_tables(int32_t model, int32_t precision, double *sta
         if (precision == 8) veryfasttree::createAAModel<double>(model, t);
         else veryfasttree::createAAModel<float>(model, t);
         aaModelOut<double>(t, stat, statinv, eigenval, codefreq, eigeninv, eigeninvT);
+        return VFT_OK;
+    } catch (const std::exception &) {
+        return VFT_ERR_INVALID;
+    }
+}
+
+/* `-trans`: the parse alone (host/ReadTransition.h), no device and no file */
+extern "C" int vft_read_aa_transition(const char *text, double *matrix, double *stat, char *err, int32_t errLen) {
+    try {
+        if (!text || !matrix || !stat) throw std::invalid_argument("vft_read_aa_transition: bad arguments");
+        double m[20][20], s[20];
+        veryfasttree::readAATransition(text, strlen(text), m, s);
+        for (int i = 0; i < 20; i++) {
+            stat[i] = s[i];
+            for (int j = 0; j < 20; j++) matrix[20 * i + j] = m[i][j];
+        }
+        return VFT_OK;
+    } catch (const std::exception &e) {
+        if (err && errLen > 0) snprintf(err, (size_t) errLen, "%s", e.what());
+        return VFT_ERR_INVALID;
+    }
+}
+
+extern "C" int vft_nj_set_aa_transition(const double *matrix, const double *stat) {
+    veryfasttree::AATransition &custom = veryfasttree::customAATransition();
+    if (!matrix && !stat) {
+        custom.set = false;
+        return VFT_OK;
+    }
+    if (!matrix || !stat) return VFT_ERR_INVALID;
+    for (int i = 0; i < 20; i++)
+        if (!(stat[i] > 0) || !std::isfinite(stat[i])) return VFT_ERR_INVALID;   /* (1 / stat and sqrt(stat) are taken) */
+    for (int i = 0; i < 400; i++)
+        if (!std::isfinite(matrix[i])) return VFT_ERR_INVALID;
+    for (int i = 0; i < 20; i++) {
+        custom.stat[i] = stat[i];
+        for (int j = 0; j < 20; j++) custom.matrix[i][j] = matrix[20 * i + j];
+    }
+    custom.set = true;
+    return VFT_OK;
+}
+
+extern "C" int vft_nj_get_aa_transition(void) { return veryfasttree::customAATransition().set ? 1 : 0; }
+
+extern "C" int vft_aa_model_matrix(int32_t model, double *matrix, double *stat) {
+    if (!matrix || !stat) return VFT_ERR_INVALID;
+    try {
+        const double *s, *flat;
+        veryfasttree::aaModelConstants(model, s, flat);
+        for (int i = 0; i < 20; i++) stat[i] = s[i];
+        for (int i = 0; i < 400; i++) matrix[i] = flat[i];
+        return VFT_OK;
+    } catch (const std::exception &) {
+        return VFT_ERR_INVALID;
+    }
+}
+
+template<typename REAL>
+static void tablesFromMatrix(const double *matrix, const double *stat, veryfasttree::TransitionTables20 &t) {
+    double m[20][20];
+    for (int i = 0; i < 20; i++)
+        for (int j = 0; j < 20; j++) m[i][j] = matrix[20 * i + j];
+    veryfasttree::createTransitionTables<REAL, 20>(m, stat, t);
+}
+
+extern "C" int vft_aa_tables_from_matrix(const double *matrix, const double *statIn, int32_t precision, double *stat, double *statinv, double *eigenval,
+                                         double *codefreq, double *eigeninv, double *eigeninvT) {
+    if (!matrix || !statIn || !stat || !statinv || !eigenval || !codefreq || !eigeninv || !eigeninvT || (precision != 4 && precision != 8)) return VFT_ERR_INVALID;
+    try {
+        veryfasttree::TransitionTables20 t;
+        if (precision == 8) tablesFromMatrix<double>(matrix, statIn, t);
+        else tablesFromMatrix<float>(matrix, statIn, t);
+        aaModelOut<double>(t, stat, statinv, eigenval, codefreq, eigeninv, eigeninvT);
+        return VFT_OK;
+    } catch (const std::exception &) {
+        return VFT_ERR_INVALID;
+    }
+}
+
+extern "C" int vft_aa_near_tables_from_matrix(const double *matrix, const double *statIn, int32_t precision, double *nearP, double *nearFreq) {
+    if (!matrix || !statIn || !nearP || !nearFreq || (precision != 4 && precision != 8)) return VFT_ERR_INVALID;
+    try {
+        veryfasttree::TransitionTables20 t;
+        veryfasttree::NearTables20 n;
+        if (precision == 8) {
+            tablesFromMatrix<double>(matrix, statIn, t);
+            veryfasttree::nearPosteriorTables<double>(t, n);
+        } else {
+            tablesFromMatrix<float>(matrix, statIn, t);
+            veryfasttree::nearPosteriorTables<float>(t, n);
+        }
+        for (int i = 0; i < 20; i++)
+            for (int j = 0; j < 20; j++) {
+                nearP[20 * i + j] = n.nearP[i][j];
+                nearFreq[20 * i + j] = n.nearFreq[i][j];
+            }
         return VFT_OK;
     } catch (const std::exception &) {
         return VFT_ERR_INVALID;

@@ -12,8 +12,10 @@ import numpy as np
 RefRun = collections.namedtuple("RefRun", "n_codes dtype n_bootstrap kwargs other")
 RefRun.__doc__ = """n_codes: 4 with -nt, else 20; dtype: np.float64 with -double-precision, else np.float32 (also kwargs["dtype"]);
 n_bootstrap: `-boot N`, 0 with -nosupport, else 1000; kwargs: the keyword arguments of nj_newick, only those the flags ask for;
-other: what nj_newick has no keyword for and the caller has to act on - makematrix, rawdist, notop (True), seed (int), log (the file
-name of `-log FILE`: this module opens no file - the caller hands it to nj_newick(log=...))."""
+other: what the caller has to act on - makematrix, notop (True), seed (int), log (the file name of `-log FILE`: this module opens no
+file - the caller hands it to nj_newick(log=...)), rawdist (True: with makematrix the matrix's own switch, else nj_newick(rawdist=True)),
+trans (the file name of `-trans FILE`: the caller reads it and hands the text to nj_newick(aa_trans=...), which then ignores aa_model,
+as the reference ignores -wag / -lg beside -trans)."""
 
 SWITCHES = ("-nt", "-double-precision", "-lg", "-wag", "-gtr", "-gamma", "-noml", "-nome", "-mllen", "-nocat", "-nosupport", "-slow",
             "-fastest", "-2nd", "-no2nd", "-notop", "-slownni", "-makematrix", "-rawdist", "-approxml", "-mlapprox")
@@ -35,7 +37,7 @@ def zero_round_stages(me_nni, spr, ml_nni, nni_rounds, ml_nni_rounds):
 
 
 def file_of(flags, flag):
-    """(the flags without `flag FILE`, FILE or None) for a flag that takes a file name (-log, -intree); a ValueError that names the flag
+    """(the flags without `flag FILE`, FILE or None) for a flag that takes a file name (-log, -intree, -trans); a ValueError that names the flag
     where the name is missing or the flag is given twice.  Callers that keep flags of their own next to the reference's (tools/nj_tree.py)
     take the file out with this before they look at the rest."""
     flags = list(flags)
@@ -91,7 +93,7 @@ def from_reference_flags(flags, threads=None, intree_text=None):
     one need the text; the text alone is taken as `-intree`.  An unknown flag, a flag without its number and a number out of range are
     a ValueError that names the flag."""
     flags, files = flags.split() if isinstance(flags, str) else list(flags), {}
-    for flag in ("-intree", "-log"):
+    for flag in ("-intree", "-log", "-trans"):
         flags, name = file_of(flags, flag)
         if name is not None:
             files[flag] = name
@@ -102,6 +104,8 @@ def from_reference_flags(flags, threads=None, intree_text=None):
     models = [m for m in ("-lg", "-wag") if m in f]
     if models and (nt or len(models) > 1):
         raise ValueError("%s is one amino-acid model: not with %s" % (models[-1], "-nt" if nt else models[0]))
+    if "-trans" in f and nt:
+        raise ValueError("-trans %s is an amino-acid model: not with -nt" % f["-trans"])   # (VeryFastTree.cpp:100)
     if not nt:
         kw["aa_model"] = models[0][1:] if models else "jtt"
     if "-slow" in f and "-fastest" in f:
@@ -150,5 +154,5 @@ def from_reference_flags(flags, threads=None, intree_text=None):
         kw["approx_ml"] = True
     kw.update({key: f[flag] for flag, key in THOROUGH.items() if f.get(flag)})   # (a count of 0 has become the switches above)
     n_bootstrap = 0 if "-nosupport" in f else f.get("-boot", 1000)
-    other = {key: f["-" + key] for key in ("makematrix", "rawdist", "notop", "seed", "log") if "-" + key in f}
+    other = {key: f["-" + key] for key in ("makematrix", "rawdist", "notop", "seed", "log", "trans") if "-" + key in f}
     return RefRun(4 if nt else 20, dtype, n_bootstrap, kw, other)
